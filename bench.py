@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: batched Board.step (BASELINE.json metric) on 1..8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+`--full` adds what the headline figure does not need (the CPU baseline: the
+oracle timed on the host).  `--dump-outputs DIR` writes what the last timed
+step returned as DIR/<name>.npy (float32; a fixed sample of 4096 envs); the
+inputs are a function of the arguments alone, so two builds can be compared
+output for output.
 
 One "step" = one TileMatchEnv.step for every env of the shard (one HIP launch
 per env group; `--groups` groups run on separate HIP streams so one group's
@@ -207,6 +214,54 @@ def load_profile(fname, run, ident):
     return prof
 
 
+DUMP_MAX_ENVS = 4096        # c5 (20x20, 760 actions): 4096 envs of float32 outputs are ~26 MB
+
+
+def step_outputs(env, venv_out, take):
+    """What the last timed step handed its caller, as named device tensors
+    with the env axis first, rows picked by `take`.  --api vector: the tuple
+    TileMatchVectorEnv.step returned.  --api raw: step_raw returns nothing, its
+    results are the env's own tensors (what TileMatchVecEnv.step returns from
+    them after join()), the effective-action bit words unpacked to a mask."""
+    import torch
+    if venv_out is not None:
+        obs, reward, terminated, truncated, infos = venv_out
+        named = {"obs_board": obs["board"], "obs_num_moves_left": obs["num_moves_left"], "reward": reward,
+                 "terminated": terminated, "truncated": truncated}
+        for key, v in infos.items():
+            if isinstance(v, dict):
+                named.update({f"info_{key}_{k2}": v2 for k2, v2 in v.items()})
+            else:
+                named["info_" + key.lstrip("_") + ("_valid" if key.startswith("_") else "")] = v
+        return {name: take(t) for name, t in named.items()}
+    named = {"obs_board": env.board, "obs_num_moves_left": env.num_moves - env.timer, "reward": env.reward,
+             "flags": env.flags, "info_num_new_specials": env.n_new, "info_num_specials_activated": env.n_act}
+    if env.actions is not None:
+        named["actions"] = env.actions                  # --policy effective: what the step sampled
+    named = {name: take(t) for name, t in named.items()}
+    eff = take(env.eff)
+    bits = torch.arange(64, device=eff.device, dtype=torch.int64)
+    named["info_action_mask"] = ((eff.unsqueeze(-1) >> bits) & 1).reshape(eff.shape[0], -1)[:, :env.num_actions]
+    return named
+
+
+def dump_outputs(dirname, env, venv_out, suffix=""):
+    """Write step_outputs as DIR/<name><suffix>.npy, float32 (every value is a
+    small integer or a bool, exact in float32).  More than DUMP_MAX_ENVS envs:
+    the same seeded sample of env rows every run, listed in env_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = env.num_envs
+    idx = np.arange(n)
+    if n > DUMP_MAX_ENVS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ENVS, replace=False))
+    dev_idx = torch.from_numpy(idx).to(env.device)
+    np.save(os.path.join(dirname, f"env_index{suffix}.npy"), idx.astype(np.float64))
+    for name, t in step_outputs(env, venv_out, lambda t: t[dev_idx]).items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), t.cpu().numpy().astype(np.float32))
+
+
 def spawn_ranks(n):
     """`bench.py --gpus n` without a launcher: start n rank processes (this
     process touches no GPU) and exit with the worst of their codes."""
@@ -257,7 +312,14 @@ def main():
     ap.add_argument("--graph", type=int, default=0,
                     help="1: the timed steps are captured into one HIP graph beforehand (TileMatchVecEnv.capture_steps: "
                          "the same launches, one host call for the whole window; --api raw)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (the oracle timed on this "
+                         "host, ~16 s; one GPU only).  A plain run sets up, warms up, times the steps and prints the line "
+                         "with cpu_baseline = null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned to its caller (board, reward, flags, "
+                         "masks ...) as DIR/<name>.npy, float32; more than 4096 envs: a fixed seeded sample of them")
     ap.add_argument("--dry-run", action="store_true", help="print each rank's shard layout and exit (no GPU)")
     args = ap.parse_args()
     if args.groups is None:
@@ -327,12 +389,16 @@ def main():
     env.status(clear=True)
 
     rows = [acts[t] for t in range(T)]                    # the staged action rows (views)
+    venv_out = None                                       # what the vector env's last step returned (--dump-outputs)
 
     def step(t, fork=True):
         # fork=False: back-to-back steps on staged actions (nothing queued on
         # the current stream in between), so the group streams skip the fork
+        nonlocal venv_out
         if venv is not None:
-            venv.step(rows[t % T])                            # obs, rewards, terminations, truncations, infos
+            out = venv.step(rows[t % T])                      # obs, rewards, terminations, truncations, infos
+            if args.dump_outputs:
+                venv_out = out
         elif args.policy == "effective":
             env.step_effective(t, first_env=rng_.start, fork=fork)   # sampled inside the step
         else:
@@ -373,6 +439,8 @@ def main():
         dist.barrier()
     el = time.perf_counter() - t0
     step_ms = ev[0].elapsed_time(ev[1]) / max(1, args.steps)
+    if args.dump_outputs:                 # the state the last timed step left, before anything else steps it
+        dump_outputs(args.dump_outputs, env, venv_out, suffix=f"_rank{rank}" if world > 1 else "")
     if graph is not None:
         # the graph's kernels run on the runtime's streams: group 0's launch
         # time from 10 eager steps after the timed window (untimed)
@@ -407,8 +475,9 @@ def main():
         per_launch_gbs = bpu * launch_envs / (kern_ms * 1e-3) / 1e9
         smask = (1 if "cookie" in cl else 0) | (2 if "vertical_laser" in co else 0) | \
                 (4 if "horizontal_laser" in co else 0) | (8 if "bomb" in co else 0)
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args.config, R, C, k, smask, moves,
-                                                                             policy=args.policy)
+        cpu = None
+        if args.full and not args.no_cpu_baseline and world == 1:
+            cpu = cpu_baseline(args.config, R, C, k, smask, moves, policy=args.policy)
         issue = None
         ident = {"build_src": build["src"][:16], "policy": args.policy, "api": args.api, "boards_per_gpu": nb,
                  "env_groups_per_gpu": env.groups, "phase_blocks": args.phase_blocks}

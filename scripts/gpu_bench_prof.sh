@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS=${BENCH_ARGS:---steps 300 --warmup 30}
+ARGS="${BENCH_ARGS:---steps 300 --warmup 30} --full"
 timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py $ARGS > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -3 gpurun_out/bench.log
 [ $rc -ne 0 ] && exit $rc

@@ -38,7 +38,7 @@ deep)
   ;;
 bench)
   for c in ${CONFIGS:-c2 c3 c5 c4}; do
-    timeout -k 10 400 python bench.py $(bargs $c) > $OUT/${c}_bench.log 2>&1 || { echo "bench $c failed"; tail $OUT/${c}_bench.log; exit 1; }
+    timeout -k 10 400 python bench.py --full $(bargs $c) > $OUT/${c}_bench.log 2>&1 || { echo "bench $c failed"; tail $OUT/${c}_bench.log; exit 1; }
     tail -1 $OUT/${c}_bench.log | cut -c1-200
   done
   timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/c2_driver_window_bench.log 2>&1 || exit 1

@@ -37,7 +37,7 @@ deep)
 bench)
   for pol in ${POLICY:-uniform}; do
     for c in ${CONFIGS:-c2 c3 c5 c4}; do
-      timeout -k 10 400 python bench.py $(bargs $c) --policy $pol ${BENCH_ARGS:-} > $OUT/${c}_${pol}_bench.log 2>&1 \
+      timeout -k 10 400 python bench.py --full $(bargs $c) --policy $pol ${BENCH_ARGS:-} > $OUT/${c}_${pol}_bench.log 2>&1 \
         || { echo "bench $c $pol failed"; tail $OUT/${c}_${pol}_bench.log; exit 1; }
       echo "$c $pol $(tail -1 $OUT/${c}_${pol}_bench.log | cut -c88-150)"
     done

@@ -27,7 +27,7 @@ prof)
 lines)
   run() {   # name, bench args...
     local name=$1; shift
-    timeout -k 10 400 python bench.py "$@" > $OUT/$name.log 2>&1 || { echo "bench $name failed"; tail $OUT/$name.log; exit 1; }
+    timeout -k 10 400 python bench.py --full "$@" > $OUT/$name.log 2>&1 || { echo "bench $name failed"; tail $OUT/$name.log; exit 1; }
     tail -1 $OUT/$name.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$name', '%.4g' % d['value'], 'ms/step', d['ms_per_step'], 'issue', (r.get('issue') or {}).get('salu_frac'), 'traffic', r.get('traffic_bytes_per_env_step'), 'cpu', (d.get('cpu_baseline') or {}).get('value'))"
   }
   run c2 ; run c2_p1 --phase-blocks 1 ; run c2_vec --api vector ; run c2_eff --policy effective

@@ -27,6 +27,18 @@ def test_gpus_n_spawns_one_rank_per_gpu():
             assert d["envs"] == [r.start, r.stop]
 
 
+def test_full_and_dump_outputs_options_parse():
+    """`--full` (off by default) and `--dump-outputs DIR` are options of the
+    plain command line; a dry run with them writes nothing."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                          "--full", "--dump-outputs", os.path.join(ROOT, "no_such_dir"), "--dry-run"],
+                         capture_output=True, text=True, timeout=300,
+                         env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK")})
+    assert out.returncode == 0, out.stderr
+    assert json.loads(out.stdout)["rank"] == 0
+    assert not os.path.exists(os.path.join(ROOT, "no_such_dir"))
+
+
 def test_staggered_phase_is_ineffective_moves():
     """bench's phase stagger (timer0 = env mod num_moves) is exactly the state
     after that many ineffective moves (board.py:352-353: no board or RNG

@@ -125,6 +125,11 @@ enum : int {
     CV_FAST,             // fast_clear step (general kernel, no specials enabled)
     CV_SHUFFLE_GEN,      // shuffle in generate_board's loop (board.py:102-106)
     CV_REJECT_GEN,       // Lemire rejection in the row-plane generate (bp_generate): exact redo
+    CV_RP_PASSES,        // row-plane cascade (rp_move): more than one gravity pass
+    CV_RP_PERP,          // rp_move: perpendicular pass took a line
+    CV_RP_VLONG,         // rp_move: vertical run longer than 3
+    CV_RP_WIDE,          // rp_refill: more than 64 colours in one refill
+    CV_RP_REJECT,        // rp_refill: Lemire rejection, serial replay
     CV_COUNT = 32
 };
 #if TMG_COVER
@@ -898,55 +903,15 @@ __device__ __forceinline__ void lds_row(const WS &w, int off, int nd, uint32_t (
     for (int i = 0; i < 8; i++) d[i] = i < nd ? __builtin_amdgcn_alignbit(raw[i + 1], raw[i], sh) : 0u;
 }
 
-// Fills w.effw (bit a = action a effective); returns 1 if any action is
-// effective, 0 if none, -1 (clean = false only) when the board is not one the
-// predicate covers — an empty cell, a coloured cookie, a colour outside 0..2^NBV-1
-// or a colour triple — and the caller must run the exact scan.  TYPES = false:
-// every type is 1 (the lean kernels).
+// The scan proper, from row r's colour-value planes X (0 outside the board,
+// masked to the row's columns cm) and, with specials, its type masks NS / CK /
+// Z.  scan_rows_nb reads them from the LDS board; the row-plane cascade
+// (tmg_rp.hip) hands over the planes it already holds.
 template <bool TYPES, int NBV, class WS>
-__device__ __forceinline__ int scan_rows_nb(const Params &P, WS &w, int lane_, bool clean) {
-    const int R = P.R, C = P.C, N = P.N;
-    const int r = loop_lane(lane_);
-    const bool on = r < R;
-    const int rr = on ? r : 0;
-    const int nd = (C + 3) >> 2;
-    // ---- row r as bit-planes (and, with specials, its special / cookie / empty masks)
-    uint32_t X[NBV];
-    bool odd = false;
-    {
-        uint32_t d[8];
-        lds_row(w, rr * C, nd, d);
-#pragma unroll
-        for (int b = 0; b < NBV; b++) X[b] = 0u;
-        uint32_t hi = 0u;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            if (j < nd) {
-#pragma unroll
-                for (int b = 0; b < NBV; b++) X[b] |= byte_bits(d[j], b) << (4 * j);
-                hi |= d[j];
-            }
-        }
-        // a colour with bits above the planes (a hand-edited board) would alias
-        if (!clean) odd = (hi & (0x01010101u * (0xFFu & (0xFFu << NBV)))) != 0u;
-    }
-    const uint32_t cm = on ? (C >= 32 ? ~0u : (1u << C) - 1u) : 0u;    // the row's columns
-#pragma unroll
-    for (int b = 0; b < NBV; b++) X[b] &= cm;
-    uint32_t NS = 0u, CK = 0u, Z = 0u;             // type not in {0, 1} / cookie (type < 0) / empty (type 0)
-    if constexpr (TYPES) {
-        uint32_t d[8];
-        lds_row(w, N + rr * C, nd, d);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            if (j < nd) {
-                NS |= byte_bits(byte_any(d[j] & 0xFEFEFEFEu), 0) << (4 * j);
-                CK |= byte_bits(d[j] >> 7, 0) << (4 * j);
-                if (!clean) Z |= byte_bits(~byte_any(d[j]), 0) << (4 * j);
-            }
-        }
-        NS &= cm; CK &= cm; Z &= cm;
-    }
+__device__ __forceinline__ int scan_rows_core(const Params &P, WS &w, int lane_, int r, bool clean, const uint32_t (&X)[NBV],
+                                              uint32_t cm, uint32_t NS, uint32_t CK, uint32_t Z, bool odd) {
+    const int R = P.R, C = P.C;
+    const int rr = r < R ? r : 0;
     // ---- rows r+1 .. r+3 (lanes off the board hold 0: colour 0 = outside)
     uint32_t X1[NBV], X2[NBV], X3[NBV];
 #pragma unroll
@@ -1029,6 +994,58 @@ __device__ __forceinline__ int scan_rows_nb(const Params &P, WS &w, int lane_, b
     put(mh, C * (R - 1) + rr * (C - 1));
     WFENCE();
     return __ballot((mv | mh) != 0u) != 0ULL ? 1 : 0;
+}
+
+// Fills w.effw (bit a = action a effective); returns 1 if any action is
+// effective, 0 if none, -1 (clean = false only) when the board is not one the
+// predicate covers — an empty cell, a coloured cookie, a colour outside 0..2^NBV-1
+// or a colour triple — and the caller must run the exact scan.  TYPES = false:
+// every type is 1 (the lean kernels).
+template <bool TYPES, int NBV, class WS>
+__device__ __forceinline__ int scan_rows_nb(const Params &P, WS &w, int lane_, bool clean) {
+    const int R = P.R, C = P.C, N = P.N;
+    const int r = loop_lane(lane_);
+    const bool on = r < R;
+    const int rr = on ? r : 0;
+    const int nd = (C + 3) >> 2;
+    // ---- row r as bit-planes (and, with specials, its special / cookie / empty masks)
+    uint32_t X[NBV];
+    bool odd = false;
+    {
+        uint32_t d[8];
+        lds_row(w, rr * C, nd, d);
+#pragma unroll
+        for (int b = 0; b < NBV; b++) X[b] = 0u;
+        uint32_t hi = 0u;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (j < nd) {
+#pragma unroll
+                for (int b = 0; b < NBV; b++) X[b] |= byte_bits(d[j], b) << (4 * j);
+                hi |= d[j];
+            }
+        }
+        // a colour with bits above the planes (a hand-edited board) would alias
+        if (!clean) odd = (hi & (0x01010101u * (0xFFu & (0xFFu << NBV)))) != 0u;
+    }
+    const uint32_t cm = on ? (C >= 32 ? ~0u : (1u << C) - 1u) : 0u;    // the row's columns
+#pragma unroll
+    for (int b = 0; b < NBV; b++) X[b] &= cm;
+    uint32_t NS = 0u, CK = 0u, Z = 0u;             // type not in {0, 1} / cookie (type < 0) / empty (type 0)
+    if constexpr (TYPES) {
+        uint32_t d[8];
+        lds_row(w, N + rr * C, nd, d);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (j < nd) {
+                NS |= byte_bits(byte_any(d[j] & 0xFEFEFEFEu), 0) << (4 * j);
+                CK |= byte_bits(d[j] >> 7, 0) << (4 * j);
+                if (!clean) Z |= byte_bits(~byte_any(d[j]), 0) << (4 * j);
+            }
+        }
+        NS &= cm; CK &= cm; Z &= cm;
+    }
+    return scan_rows_core<TYPES, NBV>(P, w, lane_, r, clean, X, cm, NS, CK, Z, odd);
 }
 
 // scan_rows_nb for the env's colour count (one instantiation survives in the
@@ -2578,6 +2595,8 @@ __device__ __forceinline__ void store_rng(uint64_t *p, const Rng &g, int lane) {
     if (lane == 0) { p[0] = g.slo; p[1] = g.shi; p[2] = g.ilo; p[3] = g.ihi; p[4] = g.h; }
 }
 
+#include "tmg_rp.hip"
+
 // TileMatchEnv.step for env e on one wave (tile_match_env.py:93-112).
 // GEN=false: lean variant for boards that can hold no special (no specials
 // enabled, cached effective mask trusted).  SBNB > 0 (<= 128 cells): the
@@ -2717,7 +2736,13 @@ __device__ __forceinline__ uint32_t step_env(
     const uint32_t bw = bwhole ? reinterpret_cast<const uint32_t *>(gb)[lane < nbw ? lane : 0] : 0u;
     const uint64_t *rp = rng + e * 5;
     const uint64_t q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3], q4 = rp[4];
-    const uint64_t *jt = P.jump + lane * 4;
+    // the row-plane cascade (tmg_rp.hip) draws in bp_ring_fill's lane order:
+    // J is then the table row of output bp_out(lane), and the rare users of
+    // the linear order below reload theirs (load_jump)
+    constexpr bool RP = SBNB > 0 && !GEN;
+    bool rowp = false;
+    if constexpr (RP) rowp = rp_shape(P);
+    const uint64_t *jt = P.jump + (rowp ? bp_out(lane) : lane) * 4;
     const uint64_t j0 = jt[0], j1 = jt[1], j2 = jt[2], j3 = jt[3];
     if (bwhole) {
         if (lane < nbw) reinterpret_cast<uint32_t *>(w.brd)[lane] = bw;
@@ -2754,8 +2779,10 @@ __device__ __forceinline__ uint32_t step_env(
     int elim = 0, nn = 0, na = 0;
     bool changed = false;
     if (effective) {
-        if constexpr (SBNB > 0 && !GEN) elim = sb_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags, e);
-        else elim = board_move<MAXN, GEN, SBNB, CODD, TIER>(P, w, lane, J, g, cl, p1, p2, flags, nn, na, e, lists,
+        if constexpr (RP) {
+            if (rowp) elim = rp_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags);
+            else elim = sb_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags, e);
+        } else elim = board_move<MAXN, GEN, SBNB, CODD, TIER>(P, w, lane, J, g, cl, p1, p2, flags, nn, na, e, lists,
                                                              trust_eff != 0);
         changed = true;
         if constexpr (GEN) {
@@ -2781,7 +2808,10 @@ __device__ __forceinline__ uint32_t step_env(
                 int fg = -1;
                 if constexpr (SBNB > 0) {
                     if (P.C <= 32) fg = bp_generate<SBNB>(P, w, lane, g);
-                    if (fg < 0) fg = sb_generate_exact<SBNB, CODD>(P, w, lane, J, g, cl);
+                    if (fg < 0) {
+                        if (rowp) J = load_jump(P, lane, g);
+                        fg = sb_generate_exact<SBNB, CODD>(P, w, lane, J, g, cl);
+                    }
                 } else {
                     fg = generate_board(P, w, lane, J, g, cl);
                 }

@@ -1,0 +1,126 @@
+"""The kernel-dispatch rule (csrc/tmg_dispatch.h): which step_kernel /
+reset_kernel instantiation a call gets, and the route around it (lean or
+general, the lane kernel, inline or deferred autoreset, the spill launch, the
+envs per wave of a reset).  The library and the host wave emulator both run
+this one rule; emu_route reports what it picks without launching anything.
+
+The expected values are written out here, read off the dispatch code as it
+stood when the rule was still spread over tmg_capi.hip, tmg_kernels.hip and
+the emulator; none is computed by the code under test."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_DIR = os.path.join(ROOT, "tools", "wave_emu")
+
+
+@pytest.fixture(scope="module")
+def emu_lib():
+    subprocess.run(["make", "-C", EMU_DIR, "libwave_emu.so"], check=True, stdout=subprocess.DEVNULL)
+    sys.path.insert(0, EMU_DIR)
+    import emu
+    return emu, emu.load()
+
+
+def fix(R, C, k, smask):
+    """A shape-specialised instantiation's FIX argument (shape_fix)."""
+    return R << 24 | C << 16 | k << 8 | smask
+
+
+NOFIX = 0
+FIX_C2 = fix(10, 10, 4, 0)
+FIX_C3 = fix(10, 10, 4, 14)          # vertical laser | horizontal laser | bomb
+FIX_C5 = fix(20, 20, 6, 15)          # every special
+FIX_RESET10 = fix(10, 10, 4, 255)    # any specials
+FIX_RESET20 = fix(20, 20, 6, 255)
+LANE = (0, 0, 0, 0, 0)               # no step_kernel instantiation: the lane kernel runs
+LANE_MIN = 131072
+FUSED = ("onehot", "terminated", "action_mask", "moves_left", "final_board", "board32")
+
+# route fields: lean, lane, deferred, kernel_autoreset, spill, reset_epw
+LEAN_INLINE = dict(lean=1, lane=0, deferred=0, kernel_autoreset=1, spill=0, reset_epw=0)
+LANE_DEFERRED = dict(lean=1, lane=1, deferred=1, kernel_autoreset=2, spill=0, reset_epw=2)
+GEN128 = dict(lean=0, lane=0, deferred=1, kernel_autoreset=2, spill=1, reset_epw=8)
+GEN512 = dict(lean=0, lane=0, deferred=1, kernel_autoreset=2, spill=1, reset_epw=2)
+LEAN512 = dict(lean=1, lane=0, deferred=1, kernel_autoreset=2, spill=0, reset_epw=2)
+
+C2 = (10, 10, 4, 0)
+# (R, C, k, smask), call (keyword arguments of emu.route), <MAXN, GEN, NB, CODD, FIX>, route
+STEPS = [
+    (C2, {}, (128, 0, 2, 0, FIX_C2), LEAN_INLINE),
+    (C2, dict(mode=2), (128, 0, 2, 0, FIX_C2), dict(LEAN_INLINE, kernel_autoreset=3)),
+    (C2, dict(n=LANE_MIN, have_lane=True), LANE, LANE_DEFERRED),
+    (C2, dict(n=LANE_MIN, have_lane=True, mode=2), LANE, dict(LANE_DEFERRED, kernel_autoreset=4)),
+    (C2, dict(n=LANE_MIN - 1, have_lane=True), (128, 0, 2, 0, FIX_C2), LEAN_INLINE),
+    (C2, dict(policy=True, have_lane=True), LANE, LANE_DEFERRED),
+    *[(C2, dict(policy=True, have_lane=True, fused=(f,)), (128, 0, 2, 0, FIX_C2), LEAN_INLINE) for f in FUSED],
+    (C2, dict(n=LANE_MIN, have_lane=True, fused=("onehot",)), (128, 0, 2, 0, FIX_C2), LEAN_INLINE),
+    (C2, dict(n=LANE_MIN, have_lane=False), (128, 0, 2, 0, FIX_C2), LEAN_INLINE),
+    (C2, dict(policy=True, have_lane=False), (128, 0, 2, 0, FIX_C2), LEAN_INLINE),
+    ((10, 10, 5, 0), dict(policy=True, have_lane=True), LANE, LANE_DEFERRED),
+    ((10, 10, 6, 0), dict(policy=True, have_lane=True), (128, 0, 3, 0, NOFIX), LEAN_INLINE),
+    (C2, dict(trust_eff=0), (128, 1, 2, 0, NOFIX), GEN128),
+    (C2, dict(trust_eff=0, policy=True, n=LANE_MIN, have_lane=True), (128, 1, 2, 0, NOFIX), GEN128),
+    ((10, 10, 4, 14), {}, (128, 1, 2, 0, FIX_C3), GEN128),
+    ((10, 10, 4, 14), dict(mode=2), (128, 1, 2, 0, FIX_C3), dict(GEN128, kernel_autoreset=4)),
+    ((10, 10, 4, 15), {}, (128, 1, 2, 0, NOFIX), GEN128),
+    ((7, 5, 5, 0), {}, (128, 0, 3, 1, NOFIX), LEAN_INLINE),
+    ((7, 5, 5, 15), {}, (128, 1, 3, 1, NOFIX), GEN128),
+    ((8, 8, 3, 0), {}, (128, 0, 2, 0, NOFIX), LEAN_INLINE),
+    ((6, 9, 9, 0), {}, (128, 0, 4, 1, NOFIX), LEAN_INLINE),
+    ((3, 4, 2, 0), {}, (128, 0, 1, 0, NOFIX), LEAN_INLINE),
+    ((2, 63, 6, 0), {}, (128, 0, 3, 1, NOFIX), LEAN_INLINE),        # bitboards up to C = 63
+    ((2, 64, 4, 0), {}, (128, 0, 0, 0, NOFIX), LEAN_INLINE),        # none at C = 64
+    ((2, 64, 4, 15), {}, (128, 1, 0, 0, NOFIX), GEN128),
+    ((20, 20, 6, 15), {}, (512, 1, 0, 0, FIX_C5), GEN512),
+    ((20, 20, 6, 0), {}, (512, 0, 0, 0, NOFIX), LEAN512),           # lean, but no inline generate at 512 cells
+    ((20, 20, 6, 0), dict(mode=2), (512, 0, 0, 0, NOFIX), dict(LEAN512, kernel_autoreset=4)),
+    ((16, 24, 7, 9), {}, (512, 1, 0, 0, NOFIX), GEN512),
+    # no autoreset: code 0, nothing deferred, whatever the kernel
+    (C2, dict(mode=0), (128, 0, 2, 0, FIX_C2), dict(LEAN_INLINE, kernel_autoreset=0)),
+    (C2, dict(mode=0, n=LANE_MIN, have_lane=True), LANE,
+     dict(LANE_DEFERRED, deferred=0, kernel_autoreset=0, reset_epw=0)),
+    ((10, 10, 4, 14), dict(mode=0), (128, 1, 2, 0, FIX_C3), dict(GEN128, deferred=0, kernel_autoreset=0, reset_epw=0)),
+    ((20, 20, 6, 15), dict(mode=0), (512, 1, 0, 0, FIX_C5), dict(GEN512, deferred=0, kernel_autoreset=0, reset_epw=0)),
+    ((20, 20, 6, 0), dict(mode=0), (512, 0, 0, 0, NOFIX), dict(LEAN512, deferred=0, kernel_autoreset=0, reset_epw=0)),
+]
+
+# (R, C, k, smask), <MAXN, NB, CODD, FIX>, envs per wave of a masked reset
+RESETS = [
+    ((10, 10, 4, 0), (128, 2, 0, FIX_RESET10), 8),
+    ((10, 10, 4, 14), (128, 2, 0, FIX_RESET10), 8),
+    ((10, 10, 5, 0), (128, 3, 0, NOFIX), 8),
+    ((20, 20, 6, 0), (512, 3, 0, FIX_RESET20), 2),
+    ((20, 20, 6, 15), (512, 3, 0, FIX_RESET20), 2),
+    ((7, 5, 5, 0), (128, 3, 1, NOFIX), 8),
+    ((6, 9, 9, 0), (128, 4, 1, NOFIX), 8),
+    ((3, 4, 2, 0), (128, 1, 0, NOFIX), 8),
+    ((2, 64, 4, 0), (128, 0, 0, NOFIX), 8),
+    ((16, 24, 7, 9), (512, 3, 0, NOFIX), 2),
+    ((9, 15, 15, 0), (512, 4, 0, NOFIX), 2),
+    ((12, 12, 2, 0), (512, 1, 0, NOFIX), 2),
+    ((12, 12, 4, 0), (512, 2, 0, NOFIX), 2),
+]
+
+
+@pytest.mark.parametrize("case", range(len(STEPS)))
+def test_step_route(emu_lib, case):
+    emu, L = emu_lib
+    shape, call, inst, want = STEPS[case]
+    got, _ = emu.route(L, *shape, **call)
+    what = f"{shape} {call}"
+    assert tuple(got[f] for f in ("MAXN", "GEN", "NB", "CODD", "FIX")) == inst, what
+    assert {f: got[f] for f in want} == want, what
+
+
+@pytest.mark.parametrize("case", range(len(RESETS)))
+def test_reset_route(emu_lib, case):
+    emu, L = emu_lib
+    shape, inst, masked = RESETS[case]
+    for call in ({}, dict(trust_eff=0), dict(mode=0), dict(policy=True, have_lane=True)):   # a reset is none of their business
+        _, got = emu.route(L, *shape, **call)
+        assert tuple(got[f] for f in ("MAXN", "NB", "CODD", "FIX")) == inst, shape
+        assert (got["epw_full"], got["epw_masked"]) == (1, masked), shape

@@ -38,7 +38,7 @@ FULL = {
     "c5": (20, 20, 6, 15, 262144, 0),
     "g1": (10, 10, 5, 0, 65536, 0),
     # one launch of 262 144 envs of the c2 shape (groups = 1): the lane-per-board
-    # kernel with given actions (tmg_capi.hip do_step, TMG_LANE_MIN_ENVS)
+    # kernel with given actions (tmg_dispatch.h route_step, kLaneMinEnvs)
     "c2x4": (10, 10, 4, 0, 262144, 0),
 }
 CASES = [("c2", "uniform"), ("c3", "uniform"), ("c4", "uniform"), ("c5", "uniform"),

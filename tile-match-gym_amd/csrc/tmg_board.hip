@@ -48,12 +48,6 @@ constexpr int kGen128Waves = 5;      // step_kernel<128, true>: c3 (96 VGPRs; 6 
 #endif
 constexpr int kReset512Waves = TMG_RESET512_WAVES;   // reset_kernel<512>: c5's regeneration (7: 0.8 % slower, profiles/r04/s7)
 constexpr int kReset128Waves = TMG_RESET128_WAVES;   // reset_kernel<128> specialised for 10x10 k4 (c3): 63 VGPRs
-// envs per wave of a masked reset_kernel launch (the deferred autoreset after a
-// general step; 29 of 30 find no finished env).  10x10 boards: 1 / 2 / 4 / 8 /
-// 16 measured c3 6.97 / 7.10 / 7.19 / 7.17 / 7.15 x 10^8; 20x20 boards, whose
-// regenerations are long: 2 (4 made the storm 4 % slower).
-constexpr int kMaskedResetEnvs128 = 8;
-constexpr int kMaskedResetEnvs512 = 2;
 constexpr int kC5StepWaves = 4;      // step_kernel<512, true> specialised for c5 (128 VGPRs; 3 measured the same)
 
 // compiler-only ordering point between a wave's LDS loads and later stores
@@ -2620,7 +2614,7 @@ __device__ __forceinline__ uint32_t step_env(
     int autoreset, L *lists) {
     const int N = P.N, W = P.W;
     // Only the 128-cell lean kernels regenerate a finished board inline
-    // (autoreset 1 / 3); do_step (tmg_capi.hip) hands every other kernel
+    // (autoreset 1 / 3); route_step (tmg_dispatch.h) hands every other kernel
     // autoreset 2 / 4, a masked reset_kernel launch after the step, so they
     // carry no generate_board code
     constexpr bool INLINE_GEN = !GEN && MAXN == 128;

@@ -1,6 +1,7 @@
 // tmg_capi.hip — extern "C" entry points of libtmg.so (declared in include/tmg.h).
 // Host code only: the kernels and their launchers live in tmg_kernels.hip
-// (one translation unit per kernel group, tmg_launch.h).
+// (one translation unit per kernel group, tmg_launch.h); which of them a call
+// gets is decided in tmg_dispatch.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -13,6 +14,7 @@
 
 #include "tmg.h"
 #include "tmg_board.hip"
+#include "tmg_dispatch.h"
 #include "tmg_launch.h"
 
 #ifndef TMG_SRC_SHA
@@ -129,78 +131,45 @@ static int set_device(tmg_ctx *ctx) {
     return 0;
 }
 
+// epw: envs per wave (reset_envs_per_wave)
 static int do_reset(tmg_ctx *ctx, const Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer,
-                    uint64_t *eff, const uint8_t *env_mask, int mask_bits, hipStream_t s, int epw_masked = 0) {
-    // a masked reset (the deferred autoreset after every general step; most
-    // find no finished env) takes several envs per wave
-    const int epw = !env_mask ? 1 : epw_masked ? epw_masked
-                  : ctx->maxn == 128 ? tmg::kMaskedResetEnvs128 : tmg::kMaskedResetEnvs512;
+                    uint64_t *eff, const uint8_t *env_mask, int mask_bits, hipStream_t s, int epw) {
     const dim3 grid = tmg::env_grid((n + epw - 1) / epw);
     if (ctx->maxn == 128) tmg::launch_reset128(ctx->sb, grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw);
     else tmg::launch_reset512(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw);
     return hip_check(hipGetLastError(), "kernel launch");
 }
 
-// a.autoreset: 0 none, 1 same step, 2 next step (tmg_plan_config); the
-// kernels' codes are 1 / 3 inline and 2 / 4 deferred (step_env)
+// a.autoreset: 0 none, 1 same step, 2 next step (tmg_plan_config); which
+// kernels run, and with which autoreset code, is route_step's decision
 static int do_step(tmg_ctx *ctx, Params P, StepArgs a, hipStream_t s) {
-    // lean kernels: no special can exist (none enabled) and the cached mask
-    // came from this library's own step / reset of the current boards
-    const bool lean = ctx->P.smask == 0 && a.trust_eff;
+    const tmg::StepRoute r = tmg::route_step(P, ctx->maxn, a.trust_eff, a.autoreset, a.n, true);
     const dim3 grid = tmg::env_grid(a.n);
-    const int mode = a.autoreset;
-    // the lane-per-board kernel (tmg_lane.h) takes the lean steps of the
-    // shapes it is built for, unless a fused output (one-hot, vector-env
-    // outputs) is asked for, when its lanes are busy: the in-kernel policy
-    // (every move effective) or a launch of >= kLaneMinEnvs envs.  With given
-    // actions on smaller launches the wave-per-board kernels are faster (a
-    // lane's wave runs as long as its longest cascade, and at c2's 65 536
-    // envs there is one such wave per SIMD: DESIGN.md §7.7)
-#ifndef TMG_LANE
-#define TMG_LANE 1
-#endif
-#ifndef TMG_LANE_MIN_ENVS
-#define TMG_LANE_MIN_ENVS 131072
-#endif
-    const bool lanek = TMG_LANE && lean && ctx->maxn == 128 && tmg::lane_shape(P) && !P.oh && !P.vo_term &&
-                       !P.vo_mask && !P.vo_left && !P.vo_final && !P.vo_obs &&
-                       (P.sample || a.n >= TMG_LANE_MIN_ENVS);
-    // the general and 512-cell kernels (and the lane kernel) leave finished
-    // boards to a reset launch masked by FL_RESET, which runs at several
-    // times their occupancy
-    const int deferred = mode && (ctx->maxn == 512 || !lean || lanek);
-    if (!lean) {
+    if (r.spill) {
         int rc = spill_for(ctx, s, a.n, &P.spill, &P.spill_ws);
         if (rc) return rc;
     }
-    a.autoreset = mode == 0 ? 0 : mode == 1 ? (deferred ? 2 : 1) : (deferred ? 4 : 3);
-    if (lanek) {
+    a.autoreset = r.kernel_autoreset;
+    if (r.lane) {
         tmg::launch_step_lane(s, P, a);
-    } else if (ctx->maxn == 128) {
-        if (lean) tmg::launch_step_lean128(ctx->sb, grid, s, P, a);
-        else if (ctx->sb && (P.C & 1)) tmg::launch_step_gen128_odd(grid, s, P, a);
-        else tmg::launch_step_gen128_even(ctx->sb, grid, s, P, a);
     } else {
-        tmg::launch_step512(!lean, grid, s, P, a);
+        switch (tmg::step_group(P, ctx->maxn, ctx->sb, r.lean)) {
+        case tmg::StepGroup::Lean128: tmg::launch_step_lean128(ctx->sb, grid, s, P, a); break;
+        case tmg::StepGroup::Gen128Even: tmg::launch_step_gen128_even(ctx->sb, grid, s, P, a); break;
+        case tmg::StepGroup::Gen128Odd: tmg::launch_step_gen128_odd(grid, s, P, a); break;
+        case tmg::StepGroup::Step512: tmg::launch_step512(!r.lean, grid, s, P, a); break;
+        }
     }
     int rc = hip_check(hipGetLastError(), "kernel launch");
     if (rc) return rc;
-    if (!lean) {                                   // re-run the steps that ran out of LDS list space
+    if (r.spill) {                                 // re-run the steps that ran out of LDS list space
         if (ctx->maxn == 128) tmg::launch_spill128(s, P, a);
         else tmg::launch_spill512(s, P, a);
         rc = hip_check(hipGetLastError(), "kernel launch");
         if (rc) return rc;
     }
-    if (!deferred) return 0;
-    // after a lane step the masked reset takes 2 envs per wave, not 8: the
-    // block storms (a whole env group's regeneration) dominate its time there
-    // (c2-eff 5.45 vs 5.19, c4-eff 9.9 vs 9.45 x 10^8 on one box; 1 / 4 in
-    // between, profiles/r06/s13/)
-#ifndef TMG_LANE_RESET_EPW
-#define TMG_LANE_RESET_EPW 2
-#endif
-    return do_reset(ctx, P, a.n, a.board, a.rng, a.timer, a.eff, a.flags, tmg::FL_RESET, s,
-                    lanek ? TMG_LANE_RESET_EPW : 0);
+    if (!r.deferred) return 0;
+    return do_reset(ctx, P, a.n, a.board, a.rng, a.timer, a.eff, a.flags, tmg::FL_RESET, s, r.reset_epw);
 }
 
 static int check_call(tmg_ctx *ctx, int64_t n) {
@@ -363,8 +332,8 @@ int new_ctx(tmg_ctx **out, int device, int rows, int cols, int colours, uint32_t
     c->device = device;
     c->d_jump = nullptr; c->d_sbrows = nullptr; c->d_status = nullptr; c->d_cover = nullptr;
     c->P = tmg::make_params(rows, cols, colours, (int)specials_mask, num_moves, nullptr);
-    c->maxn = c->P.N <= 128 ? 128 : 512;
-    c->sb = c->P.N <= 128 && c->P.C <= 63;
+    c->maxn = tmg::shape_maxn(c->P);
+    c->sb = tmg::shape_sb(c->P);
     c->scan_only = scan_only;
     rc = alloc_tables(c);
     if (rc) { free_ctx(c); return rc; }
@@ -483,7 +452,8 @@ int tmg_reset_onehot(tmg_ctx *ctx, int64_t n, int8_t *board, uint64_t *rng, int3
     Params P;
     rc = onehot_params(ctx, onehot, onehot_dtype, P);
     if (rc) return rc;
-    return do_reset(ctx, P, n, board, rng, timer, eff, env_mask, 0xFF, reinterpret_cast<hipStream_t>(stream));
+    return do_reset(ctx, P, n, board, rng, timer, eff, env_mask, 0xFF, reinterpret_cast<hipStream_t>(stream),
+                    tmg::reset_envs_per_wave(ctx->maxn, env_mask != nullptr));
 }
 
 int tmg_step(tmg_ctx *ctx, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer, const int32_t *actions,
@@ -614,13 +584,7 @@ int tmg_plan_step(tmg_plan *p, int32_t *actions, int32_t t, int trust_eff, int f
         P.pol_first = p->first_env + lo;
         P.pol_t = t;
         const hipStream_t gs = p->streams[g] ? p->streams[g] : cur;
-#ifndef TMG_GEN_SAMPLE
-#define TMG_GEN_SAMPLE 0
-#endif
-        if (P.sample && !TMG_GEN_SAMPLE && !(ctx->P.smask == 0 && trust_eff)) {
-            // the general kernels (low occupancy, long waves) take the draw
-            // from the sampler kernel ahead of them; the lean ones sample in
-            // their own prologue
+        if (tmg::sample_ahead(P, trust_eff)) {
             tmg::launch_sample_effective(gs, m, W, A, p->eff + lo * W, p->key, p->first_env + lo, t, actions + lo);
             rc = hip_check(hipGetLastError(), "kernel launch");
             if (rc) return rc;
@@ -674,7 +638,7 @@ int tmg_plan_capture(tmg_plan *p, int steps, int32_t *const *actions, const int3
     const hipStream_t cur = reinterpret_cast<hipStream_t>(stream);
     // the general kernels' spill queues must exist before the capture (no
     // allocation or synchronisation inside it)
-    if (!(p->ctx->P.smask == 0 && trust_eff)) {
+    if (!tmg::lean_step(p->ctx->P, trust_eff)) {
         for (size_t g = 0; g < p->streams.size() && !rc; g++) {
             tmg::SpillQ *q;
             void *ws;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tmg_board.hip"
+#include "tmg_dispatch.h"
 #include "tmg_launch.h"
 #if TMG_TU == 1
 #include "tmg_lane.h"
@@ -21,29 +22,20 @@ namespace tmg {
 
 namespace {
 
-template <int MAXN, bool GEN, int NB, bool CODD, int FIX = kNoFix>
-void step_one(dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
-    const size_t lds = sizeof(Ws<MAXN, GEN>);
-    hipLaunchKernelGGL((step_kernel<MAXN, GEN, NB, CODD, FIX>), grid, dim3(64), lds, s, P, a.n, a.board, a.rng,
-                       a.timer, a.actions, a.reward, a.n_new, a.n_act, a.flags, a.eff, a.trust_eff, a.autoreset);
-}
-// whether P is the shape a FIX instantiation was compiled for
-template <int FIX>
-bool is_shape(const Params &P) {
-    const int sm = (FIX & 255) == kFixAnySpecials ? kFixAnySpecials : P.smask;
-    return shape_fix(P.R, P.C, P.k, sm) == FIX;
-}
-
-// scalar-bitboard variants: NB colour planes (sb_planes(k))
-template <bool GEN, bool CODD>
-void step_sb(dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
-    switch (sb_planes(P.k)) {
-    case 1: step_one<128, GEN, 1, CODD>(grid, s, P, a); break;
-    case 2: step_one<128, GEN, 2, CODD>(grid, s, P, a); break;
-    case 3: step_one<128, GEN, 3, CODD>(grid, s, P, a); break;
-    default: step_one<128, GEN, 4, CODD>(grid, s, P, a); break;
+// The launchers the ladders of tmg_dispatch.h call: each member enqueues the
+// one instantiation the ladder picked.
+struct StepLaunch {
+    dim3 grid;
+    hipStream_t s;
+    const Params &P;
+    const StepArgs &a;
+    template <int MAXN, bool GEN, int NB, bool CODD, int FIX>
+    void step() {
+        const size_t lds = sizeof(Ws<MAXN, GEN>);
+        hipLaunchKernelGGL((step_kernel<MAXN, GEN, NB, CODD, FIX>), grid, dim3(64), lds, s, P, a.n, a.board, a.rng,
+                           a.timer, a.actions, a.reward, a.n_new, a.n_act, a.flags, a.eff, a.trust_eff, a.autoreset);
     }
-}
+};
 
 template <int MAXN>
 void spill_one(hipStream_t s, const Params &P, const StepArgs &a) {
@@ -52,19 +44,37 @@ void spill_one(hipStream_t s, const Params &P, const StepArgs &a) {
                        a.actions, a.reward, a.n_new, a.n_act, a.flags, a.eff, a.trust_eff, a.autoreset);
 }
 
-template <int MAXN, int NB, bool CODD, int FIX = kNoFix>
-void reset_one(dim3 grid, hipStream_t s, const Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer,
-               uint64_t *eff, const uint8_t *env_mask, int mask_bits, int epw) {
-    const size_t lds = sizeof(Ws<MAXN, false>);
-    hipLaunchKernelGGL((reset_kernel<MAXN, NB, CODD, FIX>), grid, dim3(64), lds, s, P, n, board, rng, timer, eff,
-                       env_mask, mask_bits, epw);
-}
+struct ResetLaunch {
+    dim3 grid;
+    hipStream_t s;
+    const Params &P;
+    int64_t n;
+    int8_t *board;
+    uint64_t *rng;
+    int32_t *timer;
+    uint64_t *eff;
+    const uint8_t *env_mask;
+    int mask_bits, epw;
+    template <int MAXN, int NB, bool CODD, int FIX>
+    void reset() {
+        const size_t lds = sizeof(Ws<MAXN, false>);
+        hipLaunchKernelGGL((reset_kernel<MAXN, NB, CODD, FIX>), grid, dim3(64), lds, s, P, n, board, rng, timer, eff,
+                           env_mask, mask_bits, epw);
+    }
+};
 
-template <int MAXN>
-void effective_one(dim3 grid, hipStream_t s, const Params &P, int64_t n, const int8_t *board, uint64_t *eff) {
-    hipLaunchKernelGGL(effective_kernel<MAXN>, grid, dim3(64), sizeof(Ws<MAXN, false>), s, P, n,
-                       board, eff);
-}
+struct EffectiveLaunch {
+    dim3 grid;
+    hipStream_t s;
+    const Params &P;
+    int64_t n;
+    const int8_t *board;
+    uint64_t *eff;
+    template <int MAXN>
+    void effective() {
+        hipLaunchKernelGGL(effective_kernel<MAXN>, grid, dim3(64), sizeof(Ws<MAXN, false>), s, P, n, board, eff);
+    }
+};
 
 }  // namespace
 
@@ -72,18 +82,13 @@ void effective_one(dim3 grid, hipStream_t s, const Params &P, int64_t n, const i
 // The lane-per-board lean step (tmg_lane.h): EPW envs per one-wave
 // workgroup (lane i < EPW = env EPW * group + i), the groups in wg_env's
 // XCD-blocked order.  Each lane keeps kLaneScratch bytes of LDS for a
-// shuffle's index array (the rare path).  A wave lasts as long as its longest
-// cascade, so a launch too small to give each SIMD two waves of 64 takes 32
-// envs per wave (c2's 21 845-env group launches: c2-eff +4.5 %; at c4's
-// 43 690 the 64-env waves are 4.5 % faster, profiles/r06/s12/).
+// shuffle's index array (the rare path).  EPW is 64, or 32 for a launch of
+// fewer than kLaneSmallEnvs envs (tmg_dispatch.h).
 #ifndef TMG_LANE_WPE
 #define TMG_LANE_WPE 0          // amdgpu_waves_per_eu(WPE, WPE) when > 0 (A/B)
 #endif
 #ifndef TMG_LANE_LDS
 #define TMG_LANE_LDS 0          // extra LDS bytes per workgroup (A/B: caps workgroups per CU)
-#endif
-#ifndef TMG_LANE_SMALL
-#define TMG_LANE_SMALL 32768    // launches below this many envs: 32 envs per wave
 #endif
 template <int R, int C, int K, int EPW>
 __global__ __launch_bounds__(64)
@@ -106,10 +111,6 @@ void lane_step_kernel(Params P_, int64_t n, int8_t *__restrict__ board, uint64_t
     if (st & lane::LS_CALLER) P.status[2] = 1u;
 }
 
-bool lane_shape(const Params &P) {
-    return P.smask == 0 && P.R == 10 && P.C == 10 && (P.k == 4 || P.k == 5);
-}
-
 template <int K, int EPW>
 void lane_one(hipStream_t s, const Params &P, const StepArgs &a) {
     const dim3 grid = env_grid((a.n + EPW - 1) / EPW);
@@ -119,24 +120,21 @@ void lane_one(hipStream_t s, const Params &P, const StepArgs &a) {
 }
 
 void launch_step_lane(hipStream_t s, const Params &P, const StepArgs &a) {
-    const bool small = a.n < TMG_LANE_SMALL;
+    const bool small = a.n < kLaneSmallEnvs;
     if (P.k == 4) small ? lane_one<4, 32>(s, P, a) : lane_one<4, 64>(s, P, a);
     else small ? lane_one<5, 32>(s, P, a) : lane_one<5, 64>(s, P, a);
 }
 
 void launch_step_lean128(bool sb, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
-    if (sb && is_shape<kFixC2>(P)) { step_one<128, false, 2, false, kFixC2>(grid, s, P, a); return; }
-    if (!sb) step_one<128, false, 0, false>(grid, s, P, a);
-    else if (P.C & 1) step_sb<false, true>(grid, s, P, a);
-    else step_sb<false, false>(grid, s, P, a);
+    StepLaunch l{grid, s, P, a};
+    step_lean128_ladder(P, sb, l);
 }
 #endif
 
 #if TMG_TU == 2
 void launch_step_gen128_even(bool sb, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
-    if (sb && is_shape<kFixC3>(P)) step_one<128, true, 2, false, kFixC3>(grid, s, P, a);
-    else if (sb) step_sb<true, false>(grid, s, P, a);
-    else step_one<128, true, 0, false>(grid, s, P, a);
+    StepLaunch l{grid, s, P, a};
+    step_gen128_even_ladder(P, sb, l);
 }
 #endif
 
@@ -147,52 +145,37 @@ void launch_spill512(hipStream_t s, const Params &P, const StepArgs &a) { spill_
 
 #if TMG_TU == 3
 void launch_step_gen128_odd(dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
-    step_sb<true, true>(grid, s, P, a);
+    StepLaunch l{grid, s, P, a};
+    step_gen128_odd_ladder(P, l);
 }
 #endif
 
 #if TMG_TU == 4
 void launch_step512(bool gen, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
-    if (gen && is_shape<kFixC5>(P)) step_one<512, true, 0, false, kFixC5>(grid, s, P, a);
-    else if (gen) step_one<512, true, 0, false>(grid, s, P, a);
-    else step_one<512, false, 0, false>(grid, s, P, a);
+    StepLaunch l{grid, s, P, a};
+    step512_ladder(P, gen, l);
 }
 
 void launch_reset512(dim3 grid, hipStream_t s, const Params &P, int64_t n, int8_t *board, uint64_t *rng,
                      int32_t *timer, uint64_t *eff, const uint8_t *env_mask, int mask_bits, int epw) {
-    // NB = colour bit-planes of the row-plane generate (bp_generate)
-    if (is_shape<kFixReset20>(P)) { reset_one<512, 3, false, kFixReset20>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); return; }
-    switch (sb_planes(P.k)) {
-    case 1: reset_one<512, 1, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    case 2: reset_one<512, 2, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    case 3: reset_one<512, 3, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    default: reset_one<512, 4, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    }
+    ResetLaunch l{grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw};
+    reset512_ladder(P, l);
 }
 void launch_effective512(dim3 grid, hipStream_t s, const Params &P, int64_t n, const int8_t *board, uint64_t *eff) {
-    effective_one<512>(grid, s, P, n, board, eff);
+    EffectiveLaunch l{grid, s, P, n, board, eff};
+    effective512_ladder(l);
 }
 #endif
 
 #if TMG_TU == 5
 void launch_reset128(bool sb, dim3 grid, hipStream_t s, const Params &P, int64_t n, int8_t *board, uint64_t *rng,
                      int32_t *timer, uint64_t *eff, const uint8_t *env_mask, int mask_bits, int epw) {
-    if (!sb) { reset_one<128, 0, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); return; }
-    if (is_shape<kFixReset10>(P)) { reset_one<128, 2, false, kFixReset10>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); return; }
-    const bool codd = P.C & 1;
-    switch (sb_planes(P.k)) {
-    case 1: codd ? reset_one<128, 1, true>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw)
-                 : reset_one<128, 1, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    case 2: codd ? reset_one<128, 2, true>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw)
-                 : reset_one<128, 2, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    case 3: codd ? reset_one<128, 3, true>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw)
-                 : reset_one<128, 3, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    default: codd ? reset_one<128, 4, true>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw)
-                  : reset_one<128, 4, false>(grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw); break;
-    }
+    ResetLaunch l{grid, s, P, n, board, rng, timer, eff, env_mask, mask_bits, epw};
+    reset128_ladder(P, sb, l);
 }
 void launch_effective128(dim3 grid, hipStream_t s, const Params &P, int64_t n, const int8_t *board, uint64_t *eff) {
-    effective_one<128>(grid, s, P, n, board, eff);
+    EffectiveLaunch l{grid, s, P, n, board, eff};
+    effective128_ladder(l);
 }
 #endif
 

@@ -1,7 +1,9 @@
 // tmg_launch.h — host-side launchers of the kernels, one group per
 // translation unit of tmg_kernels.hip (compiled once per TMG_TU value, in
 // parallel), called by tmg_capi.hip.  Each launcher enqueues its kernel(s) on
-// `s` and returns nothing; tmg_capi checks hipGetLastError afterwards.
+// `s` and returns nothing; tmg_capi checks hipGetLastError afterwards.  Which
+// group a call goes to (route_step, step_group) and which instantiation a
+// group launches (the *_ladder functions) is decided in tmg_dispatch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -30,8 +32,7 @@ dim3 env_grid(int64_t n);
 // sb: scalar-bitboard variants (C <= 63)
 void launch_step_lean128(bool sb, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a);
 // and the lane-per-board lean step (tmg_lane.h) for the shapes lane_shape
-// accepts; its autoreset codes are the deferred ones (0, 2, 4)
-bool lane_shape(const Params &P);
+// (tmg_dispatch.h) accepts; its autoreset codes are the deferred ones (0, 2, 4)
 void launch_step_lane(hipStream_t s, const Params &P, const StepArgs &a);
 constexpr int kLaneScratch = 128;      // LDS bytes per lane (a shuffle's index array, N <= 128)
 // TU 2 / 3 — general <= 128-cell step kernels, C even / odd (the

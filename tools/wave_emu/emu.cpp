@@ -3,6 +3,7 @@
 // lane, so AddressSanitizer / gdb see every LDS and global index.
 #include "hip/hip_runtime.h"
 #include "tmg_board.hip"
+#include "tmg_dispatch.h"
 
 #include <setjmp.h>
 #include <ucontext.h>
@@ -233,85 +234,62 @@ static tmg::Params make_params(int R, int C, int k, int smask, int moves, const 
 static uint64_t g_jump[tmg::kJumpRows * 4];
 static bool g_jump_init = false;
 
-static bool sb_ok(const tmg::Params &P) { return P.N <= 128 && P.C <= 63; }
-
-// step variants as tmg_capi.hip's do_step: one wave per env
+// The launchers the route and ladders of tmg_dispatch.h call (the library's
+// are in tmg_kernels.hip): each member runs the picked instantiation on
+// fibers, one wave per env.
 struct EmuStep {
-    const tmg::Params *P;
+    const tmg::Params &P;
     int64_t n;
     int8_t *board; uint64_t *rng; int32_t *timer; const int32_t *actions;
     int32_t *reward, *n_new, *n_act; uint8_t *flags; uint64_t *eff;
     int trust_eff, autoreset;
+    template <int MAXN, bool GEN, int NB, bool CODD, int FIX>
+    void step() {
+        run_blocks(n, sizeof(tmg::Ws<MAXN, GEN>), [&] { tmg::step_kernel<MAXN, GEN, NB, CODD, FIX>(P, n, board, rng, timer, actions, reward, n_new, n_act, flags, eff, trust_eff, autoreset); });
+    }
+    template <int MAXN>
+    void spill() {
+        run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<MAXN, false>), [&] { tmg::spill_kernel<MAXN>(P, n, board, rng, timer, actions, reward, n_new, n_act, flags, eff, trust_eff, autoreset); });
+    }
 };
 
-template <int MAXN, bool GEN, int NB, bool CODD, int FIX = tmg::kNoFix>
-static void emu_step_kernel(EmuStep &S) {
-    const tmg::Params &P = *S.P;
-    run_blocks(S.n, sizeof(tmg::Ws<MAXN, GEN>), [&] { tmg::step_kernel<MAXN, GEN, NB, CODD, FIX>(P, S.n, S.board, S.rng, S.timer, S.actions, S.reward, S.n_new, S.n_act, S.flags, S.eff, S.trust_eff, S.autoreset); });
-}
-// tmg_kernels.hip's is_shape: the shape-specialised instantiations the launchers pick
-template <int FIX>
-static bool emu_is_shape(const tmg::Params &P) {
-    const int sm = (FIX & 255) == tmg::kFixAnySpecials ? tmg::kFixAnySpecials : P.smask;
-    return tmg::shape_fix(P.R, P.C, P.k, sm) == FIX;
-}
-
-// spill_kernel after a general step launch, as tmg_capi.hip's do_step
-template <int MAXN>
-static void emu_spill(EmuStep &S) {
-    const tmg::Params &P = *S.P;
-    run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<MAXN, false>), [&] { tmg::spill_kernel<MAXN>(P, S.n, S.board, S.rng, S.timer, S.actions, S.reward, S.n_new, S.n_act, S.flags, S.eff, S.trust_eff, S.autoreset); });
-}
-
-template <bool GEN, bool CODD>
-static void emu_step_sb(EmuStep &S) {
-    switch (tmg::sb_planes(S.P->k)) {
-    case 1: emu_step_kernel<128, GEN, 1, CODD>(S); break;
-    case 2: emu_step_kernel<128, GEN, 2, CODD>(S); break;
-    case 3: emu_step_kernel<128, GEN, 3, CODD>(S); break;
-    default: emu_step_kernel<128, GEN, 4, CODD>(S); break;
+struct EmuReset {
+    const tmg::Params &P;
+    int64_t n;
+    int8_t *board; uint64_t *rng; int32_t *timer; uint64_t *eff;
+    const uint8_t *mask;
+    int bits, epw;
+    template <int MAXN, int NB, bool CODD, int FIX>
+    void reset() {
+        run_blocks((n + epw - 1) / epw, sizeof(tmg::Ws<MAXN, false>),
+                   [&] { tmg::reset_kernel<MAXN, NB, CODD, FIX>(P, n, board, rng, timer, eff, mask, bits, epw); });
     }
-}
+};
 
-template <int MAXN, int NB, bool CODD, int FIX = tmg::kNoFix>
-static void emu_reset_kernel(const tmg::Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer, uint64_t *eff,
-                             const uint8_t *mask, int bits) {
-    const int epw = !mask ? 1 : MAXN == 128 ? tmg::kMaskedResetEnvs128 : tmg::kMaskedResetEnvs512;   // as do_reset
-    run_blocks((n + epw - 1) / epw, sizeof(tmg::Ws<MAXN, false>),
-               [&] { tmg::reset_kernel<MAXN, NB, CODD, FIX>(P, n, board, rng, timer, eff, mask, bits, epw); });
-}
-template <bool CODD>
-static void emu_reset_sb(const tmg::Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer, uint64_t *eff,
-                         const uint8_t *mask, int bits) {
-    switch (tmg::sb_planes(P.k)) {
-    case 1: emu_reset_kernel<128, 1, CODD>(P, n, board, rng, timer, eff, mask, bits); break;
-    case 2: emu_reset_kernel<128, 2, CODD>(P, n, board, rng, timer, eff, mask, bits); break;
-    case 3: emu_reset_kernel<128, 3, CODD>(P, n, board, rng, timer, eff, mask, bits); break;
-    default: emu_reset_kernel<128, 4, CODD>(P, n, board, rng, timer, eff, mask, bits); break;
+struct EmuEffective {
+    const tmg::Params &P;
+    int64_t n;
+    const int8_t *board; uint64_t *eff;
+    template <int MAXN>
+    void effective() {
+        run_blocks(n, sizeof(tmg::Ws<MAXN, false>), [&] { tmg::effective_kernel<MAXN>(P, n, board, eff); });
     }
-}
+};
 
-// as tmg_capi.hip's do_reset
 static void emu_do_reset(const tmg::Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer, uint64_t *eff,
-                         const uint8_t *mask, int bits) {
-    if (emu_is_shape<tmg::kFixReset10>(P)) {
-        emu_reset_kernel<128, 2, false, tmg::kFixReset10>(P, n, board, rng, timer, eff, mask, bits);
-    } else if (emu_is_shape<tmg::kFixReset20>(P)) {
-        emu_reset_kernel<512, 3, false, tmg::kFixReset20>(P, n, board, rng, timer, eff, mask, bits);
-    } else if (sb_ok(P)) {
-        if (P.C & 1) emu_reset_sb<true>(P, n, board, rng, timer, eff, mask, bits);
-        else emu_reset_sb<false>(P, n, board, rng, timer, eff, mask, bits);
-    } else if (P.N <= 128) {
-        emu_reset_kernel<128, 0, false>(P, n, board, rng, timer, eff, mask, bits);
-    } else {
-        switch (tmg::sb_planes(P.k)) {
-        case 1: emu_reset_kernel<512, 1, false>(P, n, board, rng, timer, eff, mask, bits); break;
-        case 2: emu_reset_kernel<512, 2, false>(P, n, board, rng, timer, eff, mask, bits); break;
-        case 3: emu_reset_kernel<512, 3, false>(P, n, board, rng, timer, eff, mask, bits); break;
-        default: emu_reset_kernel<512, 4, false>(P, n, board, rng, timer, eff, mask, bits); break;
-        }
-    }
+                         const uint8_t *mask, int bits, int epw) {
+    EmuReset l{P, n, board, rng, timer, eff, mask, bits, epw};
+    tmg::reset_ladder(P, tmg::shape_maxn(P), tmg::shape_sb(P), l);
 }
+
+// emu_route's launcher: notes the instantiation a ladder picks, runs nothing
+struct Recorder {
+    int *out;
+    template <int MAXN, bool GEN, int NB, bool CODD, int FIX>
+    void step() { out[0] = MAXN; out[1] = GEN; out[2] = NB; out[3] = CODD; out[4] = FIX; }
+    template <int MAXN, int NB, bool CODD, int FIX>
+    void reset() { out[0] = MAXN; out[1] = NB; out[2] = CODD; out[3] = FIX; }
+};
 
 extern "C" {
 
@@ -333,36 +311,48 @@ int emu_step(int R, int C, int k, int smask, int moves, int64_t n, int8_t *board
     P.vo_left = left;
     P.vo_final = final_board;
     P.vo_obs = board32;
-    EmuStep S;
-    S.P = &P; S.n = n; S.board = board; S.rng = rng; S.timer = timer; S.actions = actions; S.reward = reward;
-    S.n_new = n_new; S.n_act = n_act; S.flags = flags; S.eff = eff; S.trust_eff = trust_eff; S.autoreset = autoreset;
-    const bool lean = smask == 0 && trust_eff;
-    // as tmg_capi.hip's do_step: the general and 512-cell kernels leave
-    // finished boards to a reset launch masked by FL_RESET
-    const int deferred = autoreset && (P.N > 128 || !lean);
-    S.autoreset = autoreset == 0 ? 0 : autoreset == 1 ? (deferred ? 2 : 1) : (deferred ? 4 : 3);
-    if (P.N <= 128) {
-        if (lean) {
-            if (sb_ok(P) && emu_is_shape<tmg::kFixC2>(P)) emu_step_kernel<128, false, 2, false, tmg::kFixC2>(S);
-            else if (!sb_ok(P)) emu_step_kernel<128, false, 0, false>(S);
-            else if (P.C & 1) emu_step_sb<false, true>(S);
-            else emu_step_sb<false, false>(S);
-        } else {
-            if (sb_ok(P) && emu_is_shape<tmg::kFixC3>(P)) emu_step_kernel<128, true, 2, false, tmg::kFixC3>(S);
-            else if (!sb_ok(P)) emu_step_kernel<128, true, 0, false>(S);
-            else if (P.C & 1) emu_step_sb<true, true>(S);
-            else emu_step_sb<true, false>(S);
-            emu_spill<128>(S);
-        }
-    } else if (lean) {
-        emu_step_kernel<512, false, 0, false>(S);
-    } else {
-        if (emu_is_shape<tmg::kFixC5>(P)) emu_step_kernel<512, true, 0, false, tmg::kFixC5>(S);
-        else emu_step_kernel<512, true, 0, false>(S);
-        emu_spill<512>(S);
+    // the library's route, but for the lane kernel, which the emulator has not
+    const int maxn = tmg::shape_maxn(P);
+    const tmg::StepRoute r = tmg::route_step(P, maxn, trust_eff, autoreset, n, false);
+    EmuStep S{P, n, board, rng, timer, actions, reward, n_new, n_act, flags, eff, trust_eff, r.kernel_autoreset};
+    tmg::step_ladder(P, maxn, tmg::shape_sb(P), r.lean, S);
+    if (r.spill) {
+        if (maxn == 128) S.spill<128>();
+        else S.spill<512>();
     }
     g_spill_total += P.spill->total;
-    if (deferred) emu_do_reset(P, n, board, rng, timer, eff, flags, tmg::FL_RESET);
+    if (r.deferred) emu_do_reset(P, n, board, rng, timer, eff, flags, tmg::FL_RESET, r.reset_epw);
+    return 0;
+}
+
+// What the rule picks for a step and for a reset of one call, nothing run.
+// fused: bit 0 the one-hot output, bits 1..5 vo_term / vo_mask / vo_left /
+// vo_final / vo_obs.  step[11]: MAXN, GEN, NB, CODD, FIX of the step kernel
+// (all 0 when the lane kernel takes the step), then lean, lane, deferred,
+// kernel_autoreset, spill, reset_epw.  reset[6]: MAXN, NB, CODD, FIX of the
+// reset kernel, then the envs per wave of a full and of a masked reset.
+int emu_route(int R, int C, int k, int smask, int trust_eff, int mode, int64_t n, int have_lane, int policy, int fused,
+              int *step, int *reset) {
+    static uint8_t out[8];                              // stands for any requested output buffer
+    tmg::Params P = tmg::make_params(R, C, k, smask, 1, nullptr);
+    P.sample = policy ? 1 : 0;
+    P.oh = fused & 1 ? out : nullptr;
+    P.vo_term = fused & 2 ? out : nullptr;
+    P.vo_mask = fused & 4 ? out : nullptr;
+    P.vo_left = fused & 8 ? reinterpret_cast<int64_t *>(out) : nullptr;
+    P.vo_final = fused & 16 ? reinterpret_cast<int8_t *>(out) : nullptr;
+    P.vo_obs = fused & 32 ? reinterpret_cast<int32_t *>(out) : nullptr;
+    const int maxn = tmg::shape_maxn(P);
+    const bool sb = tmg::shape_sb(P);
+    const tmg::StepRoute r = tmg::route_step(P, maxn, trust_eff, mode, n, have_lane != 0);
+    for (int i = 0; i < 5; i++) step[i] = 0;
+    Recorder rs{step}, rr{reset};
+    if (!r.lane) tmg::step_ladder(P, maxn, sb, r.lean, rs);
+    step[5] = r.lean; step[6] = r.lane; step[7] = r.deferred; step[8] = r.kernel_autoreset; step[9] = r.spill;
+    step[10] = r.reset_epw;
+    tmg::reset_ladder(P, maxn, sb, rr);
+    reset[4] = tmg::reset_envs_per_wave(maxn, false);
+    reset[5] = tmg::reset_envs_per_wave(maxn, true);
     return 0;
 }
 
@@ -376,26 +366,24 @@ int emu_reset(int R, int C, int k, int smask, int moves, int64_t n, int8_t *boar
               uint64_t *eff) {
     if (!g_jump_init) { tmg::build_jump_table(g_jump); g_jump_init = true; }
     tmg::Params P = make_params(R, C, k, smask, moves, g_jump);
-    emu_do_reset(P, n, board, rng, timer, eff, nullptr, 0xFF);
+    emu_do_reset(P, n, board, rng, timer, eff, nullptr, 0xFF, tmg::reset_envs_per_wave(tmg::shape_maxn(P), false));
     return 0;
 }
 
-// reset(env_mask): the masked reset_kernel launch (several envs per wave, as tmg_capi.hip do_reset)
+// reset(env_mask): the masked reset_kernel launch (several envs per wave)
 int emu_reset_masked(int R, int C, int k, int smask, int moves, int64_t n, int8_t *board, uint64_t *rng,
                      int32_t *timer, uint64_t *eff, const uint8_t *mask, int bits) {
     if (!g_jump_init) { tmg::build_jump_table(g_jump); g_jump_init = true; }
     tmg::Params P = make_params(R, C, k, smask, moves, g_jump);
-    emu_do_reset(P, n, board, rng, timer, eff, mask, bits);
+    emu_do_reset(P, n, board, rng, timer, eff, mask, bits, tmg::reset_envs_per_wave(tmg::shape_maxn(P), mask != nullptr));
     return 0;
 }
 
 int emu_effective(int R, int C, int k, int smask, int64_t n, const int8_t *board, uint64_t *eff) {
     if (!g_jump_init) { tmg::build_jump_table(g_jump); g_jump_init = true; }
     tmg::Params P = make_params(R, C, k, smask, 1, g_jump);
-    if (P.N <= 128)
-        run_blocks(n, sizeof(tmg::Ws<128, false>), [&] { tmg::effective_kernel<128>(P, n, board, eff); });
-    else
-        run_blocks(n, sizeof(tmg::Ws<512, false>), [&] { tmg::effective_kernel<512>(P, n, board, eff); });
+    EmuEffective l{P, n, board, eff};
+    tmg::effective_ladder(tmg::shape_maxn(P), l);
     return 0;
 }
 

@@ -27,7 +27,26 @@ def load(asan=False):
     L.emu_status.restype = ctypes.c_uint
     L.emu_cover.argtypes = [P, I]
     L.emu_cover.restype = None
+    L.emu_route.argtypes = [I, I, I, I, I, I, I64, I, I, I, P, P]
     return L
+
+
+STEP_ROUTE = ("MAXN", "GEN", "NB", "CODD", "FIX", "lean", "lane", "deferred", "kernel_autoreset", "spill", "reset_epw")
+RESET_ROUTE = ("MAXN", "NB", "CODD", "FIX", "epw_full", "epw_masked")
+FUSED = ("onehot", "terminated", "action_mask", "moves_left", "final_board", "board32")
+
+
+def route(L, R, C, k, smask, trust_eff=1, mode=1, n=1024, have_lane=False, policy=False, fused=()):
+    """What the dispatch rule (csrc/tmg_dispatch.h) picks for one step and one
+    reset, as two dicts keyed by STEP_ROUTE / RESET_ROUTE; nothing is run.
+    The step's instantiation fields are 0 when the lane kernel takes it.
+    fused: the names (of FUSED) of the fused outputs asked for."""
+    step = np.zeros(len(STEP_ROUTE), np.int32)
+    reset = np.zeros(len(RESET_ROUTE), np.int32)
+    bits = sum(1 << FUSED.index(f) for f in fused)
+    L.emu_route(R, C, k, smask, int(trust_eff), int(mode), int(n), int(have_lane), int(policy), bits,
+                step.ctypes.data, reset.ctypes.data)
+    return dict(zip(STEP_ROUTE, step.tolist())), dict(zip(RESET_ROUTE, reset.tolist()))
 
 
 def cover(L, clear=False):

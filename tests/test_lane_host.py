@@ -5,7 +5,10 @@ by env; every field of every env at every step must equal the oracle's
 finished board's regeneration to reset_kernel (FL_RESET); here the oracle's
 own reset of those envs stands in for that launch, as the product's reset
 kernel is checked against the oracle elsewhere (test_gpu_paths.py, the golden
-trajectories).  The GPU parity suite then checks the compiled kernel itself."""
+trajectories).  The GPU parity suite then checks the compiled kernel itself
+(tests/test_gpu_lane.py runs the crafted 10x10 states of tests/lane_cases.py,
+whose moves shuffle, on the device; here the host compile runs them first and
+its site counters show that they reach every rare branch)."""
 import ctypes
 import os
 import subprocess
@@ -137,6 +140,119 @@ def test_lane_policy_and_next_step(lane, shape):
         o.flags[idx] = 8
         pending = (o.flags & 1) != 0
         _compare(lb, o, f"{shape} next-step {t}")
+
+
+def _sites(L, clear=False):
+    """Hits of tmg_lane.h's coverage sites in the host compile, by _native.COVER_NAMES name."""
+    from tile_match_gym_amd._native import COVER_NAMES
+    out = np.zeros(8, np.int64)
+    L.lane_host_sites.argtypes = [P, I]
+    L.lane_host_sites.restype = None
+    L.lane_host_sites(_p(out), int(clear))
+    names = [nm for nm in COVER_NAMES if nm.startswith("lane_")]
+    assert names == ["lane_step", "lane_shuffle", "lane_redraw", "lane_reject", "lane_reject_redraw"]
+    return dict(zip(names, (int(x) for x in out)))
+
+
+def test_crafted_boards_pinned():
+    """tests/lane_cases.py: the construction gives 384 / 1024 boards, the oracle
+    keeps 272 / 856 — line-free, with an effective action — and each kept
+    board's idle action is ineffective."""
+    import lane_cases as lc
+    for k, raw in ((4, 384), (5, 1024)):
+        assert len(lc.raw_candidates(k)) == raw
+        boards, idle = lc.candidates(k)
+        assert boards.shape == (lc.CANDIDATES[k], 2, 10, 10)
+        assert len({b.tobytes() for b in boards}) == lc.CANDIDATES[k], "candidates repeat"
+        for b, a in zip(boards, idle):
+            assert (b[1] == 1).all() and b[0].min() >= 1 and b[0].max() <= k
+            assert orc.get_colour_lines(b, k, 0) == []
+            mask, playable = orc.effective_mask(b)
+            assert playable and 1 <= mask.sum() <= 9 and not mask[a]
+
+
+def _crafted_lane(lane, k, n, inject_seed=None):
+    """The crafted batch after the idle step, on the oracle and in the host
+    compile (a copy of the oracle's state: the idle step moves only the timer)."""
+    import lane_cases as lc
+    from rejection_states import words_rejecting_at
+    o, idle = lc.crafted_oracle(k, n, threads=8)
+    o.step(idle, autoreset=True)
+    assert (o.flags == 0).all() and (o.timer == 1).all()
+    if inject_seed is not None:
+        o.rng[:] = words_rejecting_at(o.rng, *lc.redraw_positions(n, inject_seed))
+    return o, LaneBatch(lane, o)
+
+
+@pytest.mark.parametrize("k", [4, 5])
+def test_lane_crafted_shuffles(lane, k):
+    """10x10 boards whose move shuffles (tests/lane_cases.py): shuffle,
+    interval and redraw_rows of the product shapes, then 8 more moves on the
+    shuffled boards."""
+    import lane_cases as lc
+    from oracle.policy_np import sample_effective_np
+    n = 2048
+    o, lb = _crafted_lane(lane, k, n)
+    _sites(lane, clear=True)
+    moves = shuffled = 0
+    for t in range(1, 10):
+        want_a = sample_effective_np(o.eff, lc.A, lc.KEY, 0, t)
+        st, a = lb.step(np.zeros(n, np.int32), 2, sample=1, key=lc.KEY, first=0, t=t)
+        assert st == 0 and np.array_equal(a, want_a), f"k{k} step {t}: policy actions"
+        o.step(want_a, autoreset=True)
+        _compare(lb, o, f"crafted k{k} step {t}")
+        assert not (o.flags & 0x80).any()
+        moves += int((o.reward > 0).sum())
+        if t == 1:
+            shuffled = int(((o.flags & 4) != 0).sum())
+            assert (o.reward >= 3).all(), "every crafted env's move is effective"
+            assert shuffled >= lc.MIN_SHUFFLED[k], f"k{k}: only {shuffled} envs shuffle on the oracle"
+    s = _sites(lane)
+    assert s["lane_step"] == moves
+    assert s["lane_shuffle"] >= shuffled and s["lane_redraw"] > 0, s
+
+
+def test_lane_crafted_rejections(lane):
+    """Lemire rejections of draw_code<5> (the rejected word is 0): in the refill
+    of ordinary moves (positions 0..2 of a plain rollout, injected before every
+    5th step), and in the redraws after a shuffle (positions 100..400 on the
+    crafted states)."""
+    import lane_cases as lc
+    from oracle.policy_np import sample_effective_np
+    from rejection_states import words_rejecting_at
+    from tile_match_gym_amd.seeding import batch_rng_words
+    k, n, M = 5, 2048, 10
+    o = orc.OracleBatch(10, 10, k, 0, M, batch_rng_words(range(lc.SEED0, lc.SEED0 + n)), threads=8)
+    o.reset()
+    lb = LaneBatch(lane, o)
+    rs = np.random.default_rng(k)
+    _sites(lane, clear=True)
+    for t in range(20):
+        if t % 5 == 1:
+            w = words_rejecting_at(o.rng, rs.integers(0, 3, n), buffered=rs.random(n) < 0.5)
+            o.rng[:] = w
+            lb.rng[:] = w
+        a = sample_effective_np(o.eff, lc.A, lc.KEY, 0, t)
+        st, got = lb.step(np.zeros(n, np.int32), 2, sample=1, key=lc.KEY, first=0, t=t)
+        assert st == 0 and np.array_equal(got, a)
+        reset_subset(lb, np.nonzero(lb.flags & 8)[0])
+        o.step(a, autoreset=True)
+        _compare(lb, o, f"refill rejections step {t}")
+    s = _sites(lane, clear=True)
+    assert s["lane_reject"] >= 4 * n and s["lane_reject_redraw"] == 0 and s["lane_shuffle"] == 0, s
+
+    o, lb = _crafted_lane(lane, k, n, inject_seed=77)
+    for t in range(1, 5):
+        a = sample_effective_np(o.eff, lc.A, lc.KEY, 0, t)
+        st, got = lb.step(np.zeros(n, np.int32), 2, sample=1, key=lc.KEY, first=0, t=t)
+        assert st == 0 and np.array_equal(got, a)
+        o.step(a, autoreset=True)
+        _compare(lb, o, f"redraw rejections step {t}")
+        if t == 1:
+            shuffled = int(((o.flags & 4) != 0).sum())
+            assert shuffled >= lc.MIN_SHUFFLED[k], f"only {shuffled} envs shuffle on the oracle"
+    s = _sites(lane)
+    assert s["lane_shuffle"] >= shuffled and s["lane_redraw"] > 0 and s["lane_reject_redraw"] > 0, s
 
 
 def _asan_body():

@@ -124,6 +124,11 @@ enum : int {
     CV_RP_VLONG,         // rp_move: vertical run longer than 3
     CV_RP_WIDE,          // rp_refill: more than 64 colours in one refill
     CV_RP_REJECT,        // rp_refill: Lemire rejection, serial replay
+    CV_LANE_STEP,        // lane kernel (tmg_lane.h LC_*, counted per env): an effective move ran
+    CV_LANE_SHUFFLE,     // lane kernel: shuffle in a move's ensure-playable loop
+    CV_LANE_REDRAW,      // lane kernel: redraw_rows entered
+    CV_LANE_REJECT,      // lane kernel: Lemire rejection in a refill draw
+    CV_LANE_REJECT_REDRAW,   // lane kernel: Lemire rejection in a redraw_rows draw
     CV_COUNT = 32
 };
 #if TMG_COVER

@@ -8,6 +8,14 @@
 #include "tmg_dispatch.h"
 #include "tmg_launch.h"
 #if TMG_TU == 1
+#if TMG_COVER
+// the lane kernel's sites, counted per lane: each lane is an env of its own
+#define TMG_LANE_COVER_PTR 1
+#define TMG_LANE_COVER(g, site)                                                                         \
+    do {                                                                                                \
+        if ((g).cover) atomicAdd((g).cover + (tmg::CV_LANE_STEP + (site)), 1ULL);                       \
+    } while (0)
+#endif
 #include "tmg_lane.h"
 #endif
 #if TMG_TU == 6
@@ -104,8 +112,16 @@ void lane_step_kernel(Params P_, int64_t n, int8_t *__restrict__ board, uint64_t
     const int lane = threadIdx.x & 63;
     const int64_t e = wg_env() * EPW + lane;
     if (lane >= EPW || e >= n) return;
+    static_assert(CV_LANE_STEP + lane::LC_COUNT <= CV_COUNT &&
+                      CV_LANE_REJECT_REDRAW - CV_LANE_STEP == lane::LC_REJECT_REDRAW,
+                  "CV_LANE_* follow tmg_lane.h's LC_* order");
+#if TMG_COVER
+    const lane::StepIO io{board, rng, timer, actions, reward, n_new, n_act, flags, eff,
+                          P.num_moves, autoreset, P.sample, P.pol_key, P.pol_first, P.pol_t, P.cover};
+#else
     const lane::StepIO io{board, rng, timer, actions, reward, n_new, n_act, flags, eff,
                           P.num_moves, autoreset, P.sample, P.pol_key, P.pol_first, P.pol_t};
+#endif
     const uint32_t st = lane::step_env<lane::Board<R, C, K>>(io, e, scratch + lane * kLaneScratch);
     if (st & lane::LS_INTERNAL) P.status[0] = 1u;
     if (st & lane::LS_CALLER) P.status[2] = 1u;

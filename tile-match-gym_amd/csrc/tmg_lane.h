@@ -38,11 +38,27 @@ namespace lane {
 #define TMG_LANE_NOTE_PASS() ((void)0)
 #define TMG_LANE_NOTE_HOLES(n) ((void)(n))
 #endif
+// Coverage hook of the diagnostic builds (tmg_kernels.hip under TMG_COVER,
+// tools/lane_host): site LC_* was reached by the env whose stream is g.  The
+// product build counts nothing.  A build that counts into memory defines
+// TMG_LANE_COVER_PTR: StepIO and Rng then carry the counters' address.
+#ifndef TMG_LANE_COVER
+#define TMG_LANE_COVER(g, site) ((void)0)
+#endif
 
 // flags / status bits (same values as tmg_board.hip's FL_* / ST_*)
 enum : int { LF_DONE = 1, LF_SHUF = 4, LF_RESET = 8, LF_ERR = 0x80 };
 enum : uint32_t { LS_INTERNAL = 1, LS_CALLER = 4 };
 constexpr int kLaneMaxShuffles = 1 << 12;     // kMaxShuffles
+// coverage sites (CV_LANE_* of tmg_board.hip, in this order)
+enum : int {
+    LC_STEP = 0,          // an effective move ran (step_env)
+    LC_SHUFFLE,           // shuffle in a move's ensure-playable loop
+    LC_REDRAW,            // redraw_rows entered (remove_colour_lines after a shuffle)
+    LC_REJECT,            // Lemire rejection in a refill draw
+    LC_REJECT_REDRAW,     // Lemire rejection in a redraw_rows draw
+    LC_COUNT
+};
 
 // A 128-cell bitboard.  TMG_LANE_W32 (default): four 32-bit words, so a
 // shift is one funnel shift (v_alignbit_b32) per word instead of 64-bit
@@ -173,6 +189,9 @@ TMG_LN constexpr B rect(int C, int r0, int r1, int c0, int c1) {
 struct Rng {
     uint64_t slo, shi, ilo, ihi;
     uint32_t has, buf;
+#ifdef TMG_LANE_COVER_PTR
+    unsigned long long *cover;
+#endif
 };
 TMG_LN void rng_load(Rng &g, const uint64_t *w) {
     g.slo = w[0]; g.shi = w[1]; g.ilo = w[2]; g.ihi = w[3];
@@ -200,7 +219,8 @@ TMG_LN uint32_t next32(Rng &g) {
     return (uint32_t)x;
 }
 // Generator.integers(1, K+1) - 1: numpy's buffered bounded Lemire draw
-template <int K>
+// (SITE: the coverage site of a rejected word)
+template <int K, int SITE = LC_REJECT>
 TMG_LN int draw_code(Rng &g) {
     if constexpr (K == 1) {
         return 0;                                  // rng == 0: numpy draws nothing
@@ -208,7 +228,10 @@ TMG_LN int draw_code(Rng &g) {
         constexpr uint32_t thr = (0xFFFFFFFFu - (uint32_t)(K - 1)) % (uint32_t)K;
         uint64_t m = (uint64_t)next32(g) * (uint32_t)K;
         if constexpr (thr != 0u) {
-            while ((uint32_t)m < thr) m = (uint64_t)next32(g) * (uint32_t)K;
+            while ((uint32_t)m < thr) {
+                TMG_LANE_COVER(g, SITE);
+                m = (uint64_t)next32(g) * (uint32_t)K;
+            }
         }
         return (int)(m >> 32);
     }
@@ -412,11 +435,12 @@ TMG_LN void gravity_refill(BD &b, B E, Rng &g) {
 // rows 0..row <- Generator.integers(1, k+1, (row+1)*C) (remove_colour_lines :129)
 template <class BD>
 TMG_LN void redraw_rows(BD &b, int row, Rng &g) {
+    TMG_LANE_COVER(g, LC_REDRAW);
     const int M = (row + 1) * BD::C;
     const B keep = andn(from_halves(~0ULL, ~0ULL), cells_below(M));
 #pragma unroll
     for (int k = 0; k < BD::NB; k++) b.x[k] = b.x[k] & keep;
-    for (int p = 0; p < M; p++) b.set_code(p, draw_code<BD::K>(g));
+    for (int p = 0; p < M; p++) b.set_code(p, draw_code<BD::K, LC_REJECT_REDRAW>(g));
 }
 
 // remove_colour_lines' row (board.py:126): the first line get_colour_lines
@@ -441,6 +465,7 @@ TMG_LN int first_line_row(const Det<BD> &d, int rs) {
 template <class BD>
 TMG_LN void shuffle(BD &b, Rng &g, uint8_t *ix) {
     constexpr int N = BD::N;
+    TMG_LANE_COVER(g, LC_SHUFFLE);
     for (int p = 0; p < N; p++) ix[p] = (uint8_t)p;
     for (int i = N - 1; i >= 1; i--) {
         const int j = (int)interval(g, (uint32_t)i);
@@ -666,6 +691,9 @@ struct StepIO {
     uint64_t pol_key;
     int64_t pol_first;
     int32_t pol_t;
+#ifdef TMG_LANE_COVER_PTR
+    unsigned long long *cover;
+#endif
 };
 
 // TileMatchEnv.step for env e (tile_match_env.py:93-112), the lean path with
@@ -702,6 +730,10 @@ TMG_LN uint32_t step_env(const StepIO &io, int64_t e, uint8_t *scratch) {
         unpack(b, reinterpret_cast<const uint64_t *>(io.board + e * 2 * N));
         Rng g;
         rng_load(g, io.rng + e * 5);
+#ifdef TMG_LANE_COVER_PTR
+        g.cover = io.cover;
+#endif
+        TMG_LANE_COVER(g, LC_STEP);
         int r1, c1, r2, c2;
         if (a < BD::AV) { r1 = a / BD::C; c1 = a - r1 * BD::C; r2 = r1 + 1; c2 = c1; }
         else { const int i = a - BD::AV; r1 = i / (BD::C - 1); c1 = i - r1 * (BD::C - 1); r2 = r1; c2 = c1 + 1; }

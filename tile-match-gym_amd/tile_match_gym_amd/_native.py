@@ -35,7 +35,8 @@ STATUS_INTERNAL, STATUS_OVERFLOW, STATUS_CALLER = 1, 2, 4
 COVER_NAMES = ("sb_lean", "sb_normal", "sb_laser", "sb_perp_bomb", "sb_row_bomb", "sb_closure", "sb_fallback",
                "lds_normal", "lds_laser", "lds_bomb", "lds_fallback", "serial_step", "serial_act", "serial_cookie",
                "combo", "spill", "spill_run", "shuffle", "reject", "fast", "shuffle_gen", "reject_gen",
-               "rp_passes", "rp_perp", "rp_vlong", "rp_wide", "rp_reject")
+               "rp_passes", "rp_perp", "rp_vlong", "rp_wide", "rp_reject",
+               "lane_step", "lane_shuffle", "lane_redraw", "lane_reject", "lane_reject_redraw")
 
 SPECIAL_BITS = {"cookie": 1, "vertical_laser": 2, "horizontal_laser": 4, "bomb": 8}
 FLAG_DONE, FLAG_COMBO, FLAG_SHUFFLED, FLAG_RESET, FLAG_OVERFLOW, FLAG_ERROR = 1, 2, 4, 8, 0x40, 0x80

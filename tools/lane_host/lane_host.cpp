@@ -11,6 +11,9 @@ static int g_trace_on, g_it, g_pass[64], g_holes[64];
 #define TMG_LANE_NOTE_ITERS(n) (g_iters[(n) < 63 ? (n) : 63]++)
 #define TMG_LANE_NOTE_PASS() (g_trace_on && g_it < 64 ? (void)g_pass[g_it]++ : (void)0)
 #define TMG_LANE_NOTE_HOLES(n) (g_trace_on && g_it < 64 ? (void)(g_holes[g_it++] = (n)) : (void)0)
+// hits of the coverage sites (tmg_lane.h LC_*), counted per env
+static long long g_sites[8];
+#define TMG_LANE_COVER(g, site) ((void)g_sites[site]++)
 #include "tmg_lane.h"
 
 using namespace tmg::lane;
@@ -36,6 +39,11 @@ extern "C" __attribute__((visibility("default"))) void lane_host_trace(int *out)
 
 extern "C" __attribute__((visibility("default"))) void lane_host_iters(long long *out, int clear) {
     for (int i = 0; i < 64; i++) { out[i] = g_iters[i]; if (clear) g_iters[i] = 0; }
+}
+
+extern "C" __attribute__((visibility("default"))) void lane_host_sites(long long *out, int clear) {
+    static_assert(LC_COUNT <= 8, "g_sites");
+    for (int i = 0; i < LC_COUNT; i++) { out[i] = g_sites[i]; if (clear) g_sites[i] = 0; }
 }
 
 extern "C" __attribute__((visibility("default"))) int lane_host_step(

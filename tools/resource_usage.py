@@ -49,10 +49,11 @@ def main():
         if rc:
             print(err[-3000:])
             sys.exit(1)
-    print(f"{'kernel':44s} {'TU':>2s} {'VGPR':>4s} {'SGPR':>4s} {'scr':>4s} {'occ':>3s} {'sspill':>6s}")
+    print(f"{'kernel':44s} {'TU':>2s} {'VGPR':>4s} {'SGPR':>4s} {'scr':>4s} {'occ':>3s} {'sspill':>6s} {'LDS':>6s}")
     for r in rows:
         print(f"{r['name']:44s} {r['tu']:2d} {r.get('VGPRs', 0):4d} {r.get('TotalSGPRs', 0):4d} "
-              f"{r.get('ScratchSize', 0):4d} {r.get('Occupancy', 0):3d} {r.get('SGPRsSpill', 0):6d}")
+              f"{r.get('ScratchSize', 0):4d} {r.get('Occupancy', 0):3d} {r.get('SGPRsSpill', 0):6d} "
+              f"{r.get('LDS', 0):6d}")
 
 
 if __name__ == "__main__":

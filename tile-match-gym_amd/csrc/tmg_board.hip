@@ -129,7 +129,9 @@ enum : int {
     CV_LANE_REDRAW,      // lane kernel: redraw_rows entered
     CV_LANE_REJECT,      // lane kernel: Lemire rejection in a refill draw
     CV_LANE_REJECT_REDRAW,   // lane kernel: Lemire rejection in a redraw_rows draw
-    CV_COUNT = 32
+    CV_RP_CARRY,         // rp_take: iteration served from a batch an earlier iteration drew from
+    CV_RP_REBATCH,       // rp_take: a second batch within one move
+    CV_COUNT = 40
 };
 #if TMG_COVER
 #define COVER(site)                                                                                     \
@@ -2583,6 +2585,10 @@ __device__ __forceinline__ LaneJump load_jump(const Params &P, int lane, const R
     J.Gj = U128{t[2], t[3]};
     J.incG = mul128(U128{g.ilo, g.ihi}, J.Gj);
     return J;
+}
+// the same in bp_ring_fill's lane order: the row of output bp_out(lane) (tmg_rp.hip)
+__device__ __forceinline__ LaneJump load_jump_bp(const Params &P, int lane, const Rng &g) {
+    return load_jump(P, bp_out(lane), g);
 }
 
 __device__ __forceinline__ Rng load_rng(const uint64_t *p) {

@@ -110,6 +110,55 @@ __device__ __forceinline__ uint32_t rp_slice(uint64_t lo, uint64_t hi, int s, bo
     return (uint32_t)(w0 >> sh) | (sh > 32 ? (uint32_t)(w1 << (64 - sh)) : 0u);
 }
 
+// TMG_RP_BATCH: A/B switch (0: a jump-ahead batch per cascade iteration, rp_refill;
+// 1: one per move, carried through the iterations, RpBatch)
+#ifndef TMG_RP_BATCH
+#define TMG_RP_BATCH 1
+#endif
+
+// Lemire rejection among the T colours of a refill: exact serial replay, cell
+// by cell, from the exact stream position g
+template <int NB, class WS>
+__device__ __forceinline__ void rp_replay(const Params &P, WS &w, int lane, Rng &g, uint32_t G, int pre, int T,
+                                          RowPlanes<NB> &pl) {
+    COVER(CV_REJECT);
+    COVER(CV_RP_REJECT);
+    WFENCE();
+    if (lane == 0) {
+        Rng r = g;
+        for (int i = 0; i < T; i++) w.u.draw[i] = (uint32_t)r_colour(P, r);
+        g = r;
+    }
+    rng_bcast(g);
+    WSYNC();
+    int at = pre;
+    for (uint32_t f = G; f; f &= f - 1u) {
+        const int c = __builtin_ctz(f);
+        const uint32_t code = w.u.draw[at++] - 1u;
+#pragma unroll
+        for (int b = 0; b < NB; b++) pl.p[b] |= ((code >> b) & 1u) << c;
+    }
+    WSYNC();
+}
+
+// this lane's slice sl (its colours from bit 0 up, one word per plane) into
+// its refill bits G, one run of contiguous cells at a time
+template <int NB>
+__device__ __forceinline__ void rp_deposit(uint32_t G, uint32_t (&sl)[NB], RowPlanes<NB> &pl) {
+    for (uint32_t f = G; f;) {
+        const int c = __builtin_ctz(f);
+        const int len = __builtin_ctz(~(f >> c));        // f < 2^28: a zero bit above every run
+        const uint32_t m = (1u << len) - 1u;
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            pl.p[b] |= (sl[b] & m) << c;
+            sl[b] >>= len;
+        }
+        f &= ~(m << c);
+    }
+}
+
+#if !TMG_RP_BATCH
 // The refill (board.py:233-241) of the cells G of this lane's row, T cells in
 // all, `pre` of them in the rows above: the next T colours of the env's
 // stream in row-major order.  One jump-ahead batch of 64 PCG64 outputs in
@@ -136,25 +185,7 @@ __device__ __forceinline__ void rp_refill(const Params &P, WS &w, int lane, cons
         const bool rbuf = off && (uint32_t)mbuf < P.thr;
         const bool rej = (o < n64 && (uint32_t)m0 < P.thr) || (2 * o + 1 < need && (uint32_t)m1 < P.thr);
         if (__ballot(rej) != 0ULL || rbuf) {
-            // Lemire rejection somewhere: exact serial replay, cell by cell
-            COVER(CV_REJECT);
-            COVER(CV_RP_REJECT);
-            WFENCE();
-            if (lane == 0) {
-                Rng r = g;
-                for (int i = 0; i < T; i++) w.u.draw[i] = (uint32_t)r_colour(P, r);
-                g = r;
-            }
-            rng_bcast(g);
-            WSYNC();
-            int at = pre;
-            for (uint32_t f = G; f; f &= f - 1u) {
-                const int c = __builtin_ctz(f);
-                const uint32_t code = w.u.draw[at++] - 1u;
-#pragma unroll
-                for (int b = 0; b < NB; b++) pl.p[b] |= ((code >> b) & 1u) << c;
-            }
-            WSYNC();
+            rp_replay<NB>(P, w, lane, g, G, pre, T, pl);
             return;
         }
     }
@@ -178,17 +209,7 @@ __device__ __forceinline__ void rp_refill(const Params &P, WS &w, int lane, cons
         }
         sl[b] = rp_slice(lo, hi, pre, wide);
     }
-    for (uint32_t f = G; f;) {
-        const int c = __builtin_ctz(f);
-        const int len = __builtin_ctz(~(f >> c));        // f < 2^28: a zero bit above every run
-        const uint32_t m = (1u << len) - 1u;
-#pragma unroll
-        for (int b = 0; b < NB; b++) {
-            pl.p[b] |= (sl[b] & m) << c;
-            sl[b] >>= len;
-        }
-        f &= ~(m << c);
-    }
+    rp_deposit<NB>(G, sl, pl);
     if (n64 > 0) {                                       // the stream position after the last output taken
         const int l = bp_lane(n64 - 1);
         g.slo = rdlane64(sj.lo, l);
@@ -198,16 +219,172 @@ __device__ __forceinline__ void rp_refill(const Params &P, WS &w, int lane, cons
         g.h = (uint32_t)g.h;                             // only the buffered half was used
     }
 }
+#else
+// One jump-ahead batch of 64 PCG64 outputs per move, in bp_ring_fill's lane
+// order: the next 128 colours of the env's stream (the buffered half-word
+// first, when there is one) as one wave-uniform 128-bit string per plane, bit
+// i = the i-th colour not yet taken.  Every cascade iteration takes its T
+// colours from bit 0 and shifts the strings down by T on the scalar unit
+// (Lemire rejections: the index of the first rejected word is kept beside
+// them, and an iteration that reaches it replays serially, rp_replay); the
+// env's stream position is derived from the count taken, once, when something
+// else needs it (rp_sync).
+template <int NB>
+struct RpBatch {
+    U128 sj;                     // per lane: the state after output bp_out(lane) of the batch
+    uint64_t lo[NB], hi[NB];     // wave-uniform: the planes of the colours not yet taken
+    int rfirst;                  // P.thr != 0: the batch's first Lemire-rejected word, as a colour index (else >= 128)
+    int left;                    // colours not yet taken (0: no batch)
+    int used;                    // colours taken, the buffered half-word included
+    int off;                     // the batch began with the buffered half-word
+};
+
+// the strings shifted down by the T colours taken, 1 <= T <= 128 (wave-uniform;
+// an iteration clears a line, so T >= 3).  One scalar branch on the common
+// T < 64 instead of selects per string: four shifts each.
+template <int NB>
+__device__ __forceinline__ void rp_advance(RpBatch<NB> &B, int T) {
+    if (T < 64) {
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            B.lo[b] = (B.lo[b] >> T) | (B.hi[b] << (64 - T));
+            B.hi[b] >>= T;
+        }
+    } else {
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            B.lo[b] = T < 128 ? B.hi[b] >> (T - 64) : 0ULL;
+            B.hi[b] = 0ULL;
+        }
+    }
+    B.left -= T;
+    B.used += T;
+}
+
+// a fresh batch from the stream as it stands at g (exact); J: the jump-table
+// row of output bp_out(lane)
+template <int NB>
+__device__ __forceinline__ void rp_batch(const Params &P, int lane, const LaneJump &J, const Rng &g, RpBatch<NB> &B) {
+    const uint32_t k = (uint32_t)P.k;
+    const int off = (int)(g.h >> 32) & 1;                // colour 0 is the buffered half-word
+    const uint64_t mbuf = (uint64_t)(uint32_t)g.h * k;
+    cover_uniform(P, lane, U128{g.slo, g.shi});
+    B.sj = jump128(J.Aj, U128{g.slo, g.shi}, J.incG);
+    const uint64_t out = xsl_rr(B.sj);
+    const uint64_t m0 = (uint64_t)(uint32_t)out * k, m1 = (out >> 32) * k;
+    // codes of colours l and 64 + l of the batch on lane l (bp_ring_fill); a
+    // rejected word is flagged in bit 31 of its code and travels with it
+    uint32_t c0 = (uint32_t)(m0 >> 32), c1 = (uint32_t)(m1 >> 32);
+    if (P.thr != 0u) {
+        c0 |= (uint32_t)m0 < P.thr ? 0x80000000u : 0u;
+        c1 |= (uint32_t)m1 < P.thr ? 0x80000000u : 0u;
+    }
+    const uint32_t n0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c0, 0xb1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
+    const uint32_t n1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c1, 0xb1, 0xf, 0xf, true);
+    const bool odd = lane & 1;
+    const uint32_t x0 = odd ? n1 : c0, x1 = odd ? c1 : n0;
+    const uint32_t bcode = (uint32_t)(mbuf >> 32);
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        uint64_t lo = __ballot((x0 >> b) & 1u), hi = __ballot((x1 >> b) & 1u);
+        if (off) {                                       // the buffered half-word goes first
+            hi = (hi << 1) | (lo >> 63);
+            lo = (lo << 1) | ((bcode >> b) & 1u);
+        }
+        B.lo[b] = lo;
+        B.hi[b] = hi;
+    }
+    B.rfirst = 2 * 128;
+    if (P.thr != 0u) {
+        // only the first rejected word matters: the replay that meets it drops the batch
+        const uint64_t lo = __ballot((x0 >> 31) != 0u), hi = __ballot((x1 >> 31) != 0u);
+        if (lo | hi) B.rfirst = off + (lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll(hi));
+        if (off && (uint32_t)mbuf < P.thr) B.rfirst = 0;
+    }
+    B.left = 128;
+    B.used = 0;
+    B.off = off;
+}
+
+// g <- the exact stream position after the colours taken from the batch
+// (rp_refill's / bp_ring_state's arithmetic: the state after the last output
+// touched, its high half buffered when an odd number of half-words was
+// taken); the batch is dropped
+template <int NB>
+__device__ __forceinline__ void rp_sync(RpBatch<NB> &B, Rng &g) {
+    if (B.used > 0) {
+        const int need = B.used - B.off;                 // half-words taken from the batch's outputs
+        if (need > 0) {
+            const int l = bp_lane(((need + 1) >> 1) - 1);
+            const U128 s{rdlane64(B.sj.lo, l), rdlane64(B.sj.hi, l)};
+            g.slo = s.lo;
+            g.shi = s.hi;
+            g.h = ((uint64_t)(need & 1) << 32) | (uint32_t)(xsl_rr(s) >> 32);
+        } else {
+            g.h = (uint32_t)g.h;                         // only the buffered half was used
+        }
+    }
+    B.left = 0;
+    B.used = 0;
+}
+
+// The refill (board.py:233-241) of the cells G of this lane's row, T cells in
+// all, `pre` of them in the rows above: the next T colours of the env's
+// stream in row-major order, from the move's batch.  Each lane takes its
+// slice of the strings and deposits it at its refill bits.
+template <int NB, class WS>
+__device__ __forceinline__ void rp_take(const Params &P, WS &w, int lane, RpBatch<NB> &B, Rng &g, uint32_t G, int pre,
+                                        int T, RowPlanes<NB> &pl) {
+#pragma unroll
+    for (int b = 0; b < NB; b++) pl.p[b] &= ~G;
+    if (P.k == 1) return;                                // rng == 0: numpy draws nothing, every colour is 1
+    if (B.left < T) {
+        // the batch has run out (rare: > 128 colours in one move), or a replay
+        // dropped it: a fresh one from the exact position, its jump-table row
+        // reloaded instead of kept across the cascade.  T <= 128: it fits.
+        if (B.used > 0) COVER(CV_RP_REBATCH);
+        rp_sync(B, g);
+        const LaneJump J = load_jump_bp(P, lane, g);
+        rp_batch<NB>(P, lane, J, g, B);
+    } else if (B.used > 0) {
+        COVER(CV_RP_CARRY);
+    }
+    if (P.thr != 0u) {
+        // a rejected word among the T taken: the words after it shift, so
+        // replay from the exact position and drop the batch
+        if (B.used + T > B.rfirst) {
+            rp_sync(B, g);
+            rp_replay<NB>(P, w, lane, g, G, pre, T, pl);
+            return;
+        }
+    }
+    const bool wide = T > 64;                            // wave-uniform
+    if (wide) COVER(CV_RP_WIDE);
+    uint32_t sl[NB];
+#pragma unroll
+    for (int b = 0; b < NB; b++) sl[b] = rp_slice(B.lo[b], B.hi[b], pre, wide);
+    rp_advance(B, T);
+    rp_deposit<NB>(G, sl, pl);
+}
+#endif
 
 // Board.move, board.py:330-395, for a board that can hold no special, on row
 // planes — the effectiveness test (:352) is the caller's.  J: the jump-table
-// row of output bp_out(lane) (rp_refill).  Returns eliminations; leaves the
+// row of output bp_out(lane) (rp_batch).  Returns eliminations; leaves the
 // final board in LDS and its effective mask in w.effw.
 template <int NB, bool CODD, class WS>
 __device__ __forceinline__ int rp_move(const Params &P, WS &w, int lane, const LaneJump &J, Rng &g,
                                        const Cells<WS::NP> &cl, int p1, int p2, int &flags) {
     const int R = P.R, C = P.C;
     int8_t *col = w.brd;
+#if TMG_RP_BATCH
+    // Every move that gets here clears a line (the cached mask said so, or
+    // eff_exact did), so its first refill is certain: the move's batch is
+    // issued ahead of the swap, where its multiply chain overlaps the LDS round
+    // trips below.  J is not used after it.
+    RpBatch<NB> B{};
+    if (P.k != 1) rp_batch<NB>(P, lane, J, g, B);
+#endif
     if (lane == 0) {                                     // swap_coords :355 (types are all 1)
         int8_t x = col[p1]; col[p1] = col[p2]; col[p2] = x;
     }
@@ -282,8 +459,14 @@ __device__ __forceinline__ int rp_move(const Params &P, WS &w, int lane, const L
         const uint32_t inc = rp_sum_above((uint32_t)n);
         const int T = __builtin_amdgcn_readlane((int)inc, kRpMaxR - 1);
         elim += T;                                       // R*C - nnz(type) after the resolve (:374)
+#if TMG_RP_BATCH
+        rp_take<NB>(P, w, lane, B, g, G, (int)inc - n, T, pl);
+    }
+    rp_sync(B, g);                                       // exact before the shuffle, a regeneration, store_rng
+#else
         rp_refill<NB>(P, w, lane, J, g, G, (int)inc - n, T, pl);
     }
+#endif
     // :381-391, from the planes: the effective mask of the final board; the
     // board to LDS for the write-back; the rare shuffle on the scalar bitboards
     const int any = rp_scan<NB>(P, w, lane, pl, cm);

@@ -36,7 +36,8 @@ COVER_NAMES = ("sb_lean", "sb_normal", "sb_laser", "sb_perp_bomb", "sb_row_bomb"
                "lds_normal", "lds_laser", "lds_bomb", "lds_fallback", "serial_step", "serial_act", "serial_cookie",
                "combo", "spill", "spill_run", "shuffle", "reject", "fast", "shuffle_gen", "reject_gen",
                "rp_passes", "rp_perp", "rp_vlong", "rp_wide", "rp_reject",
-               "lane_step", "lane_shuffle", "lane_redraw", "lane_reject", "lane_reject_redraw")
+               "lane_step", "lane_shuffle", "lane_redraw", "lane_reject", "lane_reject_redraw",
+               "rp_carry", "rp_rebatch")
 
 SPECIAL_BITS = {"cookie": 1, "vertical_laser": 2, "horizontal_laser": 4, "bomb": 8}
 FLAG_DONE, FLAG_COMBO, FLAG_SHUFFLED, FLAG_RESET, FLAG_OVERFLOW, FLAG_ERROR = 1, 2, 4, 8, 0x40, 0x80
@@ -225,10 +226,10 @@ class Context:
         if fn is None:
             raise TmgError("this context's library is not a TMG_COVER build")
         import numpy as np
-        out = np.zeros(32, np.uint64)
+        out = np.zeros(len(COVER_NAMES), np.uint64)
         fn.argtypes = [P, P, I, I]
         fn.restype = I
-        check(fn(self._h, out.ctypes.data, 32, int(clear)), L)
+        check(fn(self._h, out.ctypes.data, out.size, int(clear)), L)
         return out
 
     def sample_effective(self, n, eff, key, first_env, t, actions, stream):

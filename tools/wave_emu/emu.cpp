@@ -357,6 +357,7 @@ int emu_route(int R, int C, int k, int smask, int trust_eff, int mode, int64_t n
 }
 
 unsigned long long emu_spills(void) { return g_spill_total; }
+int emu_cover_count(void) { return tmg::CV_COUNT; }
 void emu_cover(unsigned long long *out, int clear) {
     for (int i = 0; i < tmg::CV_COUNT; i++) { out[i] = g_cover[i]; if (clear) g_cover[i] = 0; }
 }

@@ -51,7 +51,7 @@ def route(L, R, C, k, smask, trust_eff=1, mode=1, n=1024, have_lane=False, polic
 
 def cover(L, clear=False):
     """The CV_* branch counters of the emulated kernels (the emulator is built with TMG_COVER)."""
-    out = np.zeros(32, np.uint64)
+    out = np.zeros(L.emu_cover_count(), np.uint64)
     L.emu_cover(out.ctypes.data, int(clear))
     return out
 

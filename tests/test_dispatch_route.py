@@ -124,3 +124,67 @@ def test_reset_route(emu_lib, case):
         _, got = emu.route(L, *shape, **call)
         assert tuple(got[f] for f in ("MAXN", "NB", "CODD", "FIX")) == inst, shape
         assert (got["epw_full"], got["epw_masked"]) == (1, masked), shape
+
+
+# Every instantiation the ladders of csrc/tmg_dispatch.h name, written out by
+# hand from that file.  step: <MAXN, GEN, NB, CODD, FIX>
+ALL_STEPS = {
+    # step_lean128_ladder: no bitboards (C = 64), c2, then NB x CODD
+    (128, 0, 0, 0, NOFIX), (128, 0, 2, 0, FIX_C2),
+    (128, 0, 1, 0, NOFIX), (128, 0, 2, 0, NOFIX), (128, 0, 3, 0, NOFIX), (128, 0, 4, 0, NOFIX),
+    (128, 0, 1, 1, NOFIX), (128, 0, 2, 1, NOFIX), (128, 0, 3, 1, NOFIX), (128, 0, 4, 1, NOFIX),
+    # step_gen128_even_ladder: no bitboards, c3, NB
+    (128, 1, 0, 0, NOFIX), (128, 1, 2, 0, FIX_C3),
+    (128, 1, 1, 0, NOFIX), (128, 1, 2, 0, NOFIX), (128, 1, 3, 0, NOFIX), (128, 1, 4, 0, NOFIX),
+    # step_gen128_odd_ladder
+    (128, 1, 1, 1, NOFIX), (128, 1, 2, 1, NOFIX), (128, 1, 3, 1, NOFIX), (128, 1, 4, 1, NOFIX),
+    # step512_ladder: lean, c5, general
+    (512, 0, 0, 0, NOFIX), (512, 1, 0, 0, FIX_C5), (512, 1, 0, 0, NOFIX),
+}
+# reset: <MAXN, NB, CODD, FIX>
+ALL_RESETS = {
+    # reset128_ladder: no bitboards, 10x10 k4, NB x CODD
+    (128, 0, 0, NOFIX), (128, 2, 0, FIX_RESET10),
+    (128, 1, 0, NOFIX), (128, 2, 0, NOFIX), (128, 3, 0, NOFIX), (128, 4, 0, NOFIX),
+    (128, 1, 1, NOFIX), (128, 2, 1, NOFIX), (128, 3, 1, NOFIX), (128, 4, 1, NOFIX),
+    # reset512_ladder: 20x20 k6, NB
+    (512, 3, 0, FIX_RESET20),
+    (512, 1, 0, NOFIX), (512, 2, 0, NOFIX), (512, 3, 0, NOFIX), (512, 4, 0, NOFIX),
+}
+
+
+def test_every_instantiation_is_run(emu_lib):
+    """The shape lists of the GPU parity suites (test_gpu_parity's random-action
+    rollouts, test_gpu_paths, the row-plane shapes, tests/dispatch_cases.py),
+    with an untrusted mask where a test steps hand-set boards, launch every
+    step_kernel and reset_kernel instantiation the ladders name, but for the
+    one documented in dispatch_cases.NEVER_RUN_RESETS; and the bitboard lean
+    cascade (sb_move: lean shapes outside the row-plane limits) keeps at least
+    four shapes that can hold a vertical line."""
+    import dispatch_cases as dc
+    import rowplane_cases
+    import test_gpu_parity
+    import test_gpu_paths
+    emu, L = emu_lib
+    assert len(ALL_STEPS) == 23 and len(ALL_RESETS) == 15
+    trusted = [c[:4] for c in test_gpu_parity.RANDOM_ACTION_CFGS]
+    trusted += [v[:4] for v in test_gpu_paths.VARIANTS.values()]
+    trusted += [(R, C, k, 0) for R, C, k in rowplane_cases.SHAPES]
+    trusted += dc.CASES + [dc.ROW_PLANE_CONTROL]
+    # test_gpu_rowplane.test_crafted_boards, test_gpu_dispatch_cover.test_crafted_tall_wide: the mask step
+    untrusted = [(rowplane_cases.R10, rowplane_cases.C10, rowplane_cases.K10, 0)] + dc.CRAFTED_SHAPES
+    steps, resets, sb_move = set(), set(), set()
+    for shape, call in [(s, {}) for s in trusted] + [(s, dict(trust_eff=0)) for s in untrusted]:
+        st, rt = emu.route(L, *shape, **call)
+        assert not st["lane"]
+        steps.add(tuple(st[f] for f in ("MAXN", "GEN", "NB", "CODD", "FIX")))
+        resets.add(tuple(rt[f] for f in ("MAXN", "NB", "CODD", "FIX")))
+        R, C = shape[:2]
+        if st["lean"] and st["MAXN"] == 128 and st["NB"] > 0 and not (R <= 16 and C <= 28) and R >= 3:
+            sb_move.add(shape)
+    never = {(m, nb, codd, NOFIX) for m, nb, codd, _ in dc.NEVER_RUN_RESETS}
+    assert len(never) <= 1 and never <= ALL_RESETS
+    assert steps == ALL_STEPS, f"never launched: {sorted(ALL_STEPS - steps)}, not in the ladders: {sorted(steps - ALL_STEPS)}"
+    assert resets == ALL_RESETS - never, (f"never launched: {sorted(ALL_RESETS - never - resets)}, "
+                                          f"not expected: {sorted(resets - (ALL_RESETS - never))}")
+    assert len(sb_move) >= 4, sorted(sb_move)

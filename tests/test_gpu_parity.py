@@ -157,7 +157,7 @@ def test_generate_golden_gpu():
             assert np.array_equal(b[i], r["out"]), f"shape {(R, C, k, sm)} rec {i}"
 
 
-@pytest.mark.parametrize("cfg", [
+RANDOM_ACTION_CFGS = [
     # R, C, k, smask, n_envs, steps
     (10, 10, 4, 0, 8192, 65),
     (10, 10, 4, 14, 4096, 65),
@@ -168,7 +168,9 @@ def test_generate_golden_gpu():
     (8, 8, 3, 15, 4096, 65),
     (5, 5, 3, 15, 4096, 65),
     (6, 7, 5, 1, 2048, 45),
-    # scalar-bitboard lean path (no specials, <= 128 cells): odd C, 1..4 colour planes, C = 63
+    # lean kernels of <= 128 cells (no specials): odd C, 1..4 colour planes, C = 63.  All but
+    # 2x63 run the row-plane cascade (R <= 16, C <= 28); the bitboard cascade (sb_move) has
+    # tests/test_gpu_dispatch_cover.py
     (7, 5, 3, 0, 4096, 65),
     (6, 9, 9, 0, 2048, 45),
     (16, 8, 5, 0, 2048, 45),
@@ -183,7 +185,10 @@ def test_generate_golden_gpu():
     # bench.py's generic-shape configs g1 / g2 (no shape-specialised kernel)
     (10, 10, 5, 0, 4096, 65),
     (20, 20, 6, 14, 512, 35),
-])
+]
+
+
+@pytest.mark.parametrize("cfg", RANDOM_ACTION_CFGS)
 def test_oracle_parity_random_actions(cfg):
     """Batched random-action rollouts with autoreset vs the CPU oracle, every step."""
     from tile_match_gym_amd.vec_env import TileMatchVecEnv

@@ -29,6 +29,7 @@ import pytest
 import torch
 
 from deep_rollouts import COVER_LIB, specials
+from dispatch_cases import MASKED_RESET
 from oracle import oracle as orc
 from rejection_states import words_rejecting_at
 
@@ -134,8 +135,10 @@ def test_rare_paths_taken(name):
     env.close()
 
 
-# (R, C, k, smask): the lean 128-cell reset, the 10x10 k4 reset specialised for c3, the c5 reset
-MASKED = [(5, 6, 7, 0), (10, 10, 4, 14), (20, 20, 6, 15)]
+# (R, C, k, smask): the lean 128-cell reset, the 10x10 k4 reset specialised for c3, the c5 reset;
+# then reset<128,0> (C = 64), a tall board, the draw-by-draw generate of C > 32,
+# reset<512,2> and the smallest 512-cell board (tests/dispatch_cases.py)
+MASKED = [(5, 6, 7, 0), (10, 10, 4, 14), (20, 20, 6, 15)] + MASKED_RESET
 
 
 @pytest.mark.parametrize("shape", MASKED)

@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+from dispatch_cases import CASES as DISPATCH_CASES
 from golden_io import load_traj, traj_names, replay_trajectory
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,8 +56,9 @@ def test_trajectory_golden_emulated(emu_lib, name, autoreset, monkeypatch):
 
 
 @pytest.mark.parametrize("cfg", [
-    # R, C, k, smask: the scalar-bitboard lean path (even/odd C, 1..4 colour planes,
-    # 128 cells, C = 63) and the general kernel with specials
+    # R, C, k, smask: the lean kernels (even/odd C, 1..4 colour planes, 128 cells, C = 63):
+    # all but 2x63 run the row-plane cascade (R <= 16, C <= 28), 2x63 the bitboard one
+    # (sb_move); and the general kernel with specials
     (10, 10, 4, 0), (8, 8, 3, 0), (7, 5, 5, 0), (6, 9, 9, 0), (3, 4, 2, 0), (16, 8, 4, 0), (2, 63, 6, 0),
     (11, 11, 4, 0), (10, 10, 4, 14), (8, 8, 3, 15), (5, 12, 6, 15),
     # 512-cell kernels: rows straddle the 64-cell passes unevenly (bounded line search)
@@ -64,6 +66,9 @@ def test_trajectory_golden_emulated(emu_lib, name, autoreset, monkeypatch):
     # 512-cell general kernels with specials: wave-parallel simple / laser steps
     # (simple_step_lds) beside the lane-0 list machinery
     (20, 20, 6, 15), (12, 12, 5, 15), (16, 16, 6, 6),
+    # tall and wide boards on sb_move and the general bitboard kernels, the plane counts,
+    # C = 64 and the smallest 512-cell boards (tests/dispatch_cases.py)
+    *DISPATCH_CASES,
 ])
 def test_random_rollouts_emulated(emu_lib, cfg):
     """Random-action rollouts with autoreset: emulated kernels vs the oracle, every field, every step."""

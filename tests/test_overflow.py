@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from adversarial import MODES, adversarial_boards, effective_actions
+from dispatch_cases import CASES as DISPATCH_CASES
 from oracle import oracle as orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,7 +45,8 @@ def emu_lib():
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("R,C,k,sm", SHAPES)
+# the emulator also takes the tall, wide and few-colour boards of tests/dispatch_cases.py with specials
+@pytest.mark.parametrize("R,C,k,sm", SHAPES + [s for s in DISPATCH_CASES if s[3] != 0])
 def test_spill_path_emulated(emu_lib, mode, R, C, k, sm):
     """The kernel source on the host wave emulator (CPU): step + spill_kernel vs the oracle."""
     from tile_match_gym_amd.seeding import batch_rng_words

@@ -102,6 +102,45 @@ TMG_API int tmg_step(tmg_ctx *ctx, int64_t n, int8_t *board, uint64_t *rng, int3
              const int32_t *actions, int32_t *reward, int32_t *n_new, int32_t *n_act,
              uint8_t *flags, uint64_t *eff, int trust_eff, int autoreset, void *stream);
 
+/* What tmg_step(actions[i] = a) would report for env i, for every action a in
+ * [0, A) at once, from the current state and without changing it: Board.move
+ * (board.py:330-395) run on a copy of the board with a copy of the env's RNG
+ * stream.  Reads board, rng and (trust_eff != 0) eff; writes only the outputs,
+ * each [n][A] (or [n]) and each optional.
+ *   Ineffective actions (board.py:352-353): reward 0, n_new 0, n_act 0, flags 0.
+ *   best_action: the lowest action index among those of maximal reward over
+ *     all A actions; an env with no effective action gets action 0, reward 0.
+ *   The timer is neither read nor written and TMG_FLAG_DONE / TMG_FLAG_RESET
+ *     are never set: peek describes the move, not the episode.  With trust_eff
+ *     != 0 a finished env of a no-autoreset batch has an all-zero mask, so all
+ *     its outputs are zero.
+ *   trust_eff: as tmg_step.  Non-zero: eff is this library's mask of these
+ *     boards (the lean kernels run when no special is enabled; the first line
+ *     search is bounded).  Zero: eff may be NULL; the mask of each board is
+ *     scanned as it stands and the general kernels run, so hand-edited boards
+ *     work, including boards that already hold a line.
+ *   rng is only read.  The envs' own array answers "what will this move
+ *     return" exactly (an oracle-greedy policy: it sees the refills the env
+ *     will really draw).  Any other [n][5] array of PCG64 words gives an
+ *     honest sampled lookahead, whose refills are not the ones the env will
+ *     draw: the fair baseline.
+ *   Errors as for a step: bit 7 of that action's flags entry and
+ *     TMG_STATUS_INTERNAL in the sticky status.  A lean launch that meets a
+ *     non-normal tile flags every action of that env and raises
+ *     TMG_STATUS_INTERNAL.
+ *   n == 0 is a no-op; a tmg_create_scan context refuses the call.  Envs one
+ *     of whose actions outgrew the kernels' LDS lists are re-run whole on the
+ *     worst-case lists and count in tmg_spills. */
+TMG_API int tmg_peek(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, const uint64_t *eff,
+                     int trust_eff,
+                     int32_t *reward,       /* [n][A] num_eliminations             or NULL */
+                     int32_t *n_new,        /* [n][A]                              or NULL */
+                     int32_t *n_act,        /* [n][A]                              or NULL */
+                     uint8_t *flags,        /* [n][A] TMG_FLAG_COMBO | SHUFFLED | ERROR, or NULL */
+                     int32_t *best_action,  /* [n] lowest a of maximal reward      or NULL */
+                     int32_t *best_reward,  /* [n] that reward                     or NULL */
+                     void *stream);
+
 /* Step plans: one host call per batched step of a fixed set of buffers
  * (TileMatchEnv.step, tile_match_env.py:93-124, for every env of the batch),
  * with the batch split into env groups on their own streams, the callers'

@@ -1,0 +1,111 @@
+"""tmg_peek on the host wave emulator (CPU): the peek kernels of
+csrc/tmg_peek.hip, picked by peek_ladder (csrc/tmg_dispatch.h) and followed by
+the peek spill pass, against the oracle's Board.move of every (env, action)
+(tests/peek_cases.py oracle_peek).  Counts are compared as integers; nothing
+here has a tolerance."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import dispatch_cases
+import peek_cases
+from adversarial import MODES, adversarial_boards
+from peek_cases import assert_peek_equal, oracle_peek
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_DIR = os.path.join(ROOT, "tools", "wave_emu")
+
+
+@pytest.fixture(scope="module")
+def emu_lib():
+    subprocess.run(["make", "-C", EMU_DIR, "libwave_emu.so"], check=True, stdout=subprocess.DEVNULL)
+    sys.path.insert(0, EMU_DIR)
+    import emu
+    return emu, emu.load()
+
+
+@pytest.mark.parametrize("shape", peek_cases.SHAPES, ids=peek_cases.case_id)
+def test_peek_vs_oracle(emu_lib, shape):
+    """After a reset and after 7 uniform-random steps (boards that hold
+    specials), with the envs' own RNG words and with words of other seeds."""
+    from tile_match_gym_amd.seeding import batch_rng_words
+    emu, L = emu_lib
+    R, C, k, sm = shape
+    n = peek_cases.envs_of(shape)
+    other = batch_rng_words(range(7000, 7000 + n))
+    for steps in (7, 0):
+        o = peek_cases.rolled_batch(shape, range(500, 500 + n), steps=steps)
+        before = (o.board.copy(), o.rng.copy(), o.eff.copy())
+        for rng in (o.rng, other):
+            got = emu.peek(L, R, C, k, sm, o.board, rng, o.eff, trust_eff=1)
+            assert_peek_equal(got, oracle_peek(o.board, rng, k, sm), f"{shape} steps={steps}")
+        assert all(np.array_equal(x, y) for x, y in zip(before, (o.board, o.rng, o.eff)))
+    assert L.emu_status() == 0
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("shape", peek_cases.ADVERSARIAL_SHAPES, ids=peek_cases.case_id)
+def test_peek_untrusted_and_spill(emu_lib, mode, shape):
+    """Hand-written boards (they may hold lines and any special), no mask
+    given: the kernel scans its own, the general kernels run, and an env one
+    of whose actions outgrows the LDS lists is re-run whole by the spill pass."""
+    from tile_match_gym_amd.seeding import batch_rng_words
+    emu, L = emu_lib
+    R, C, k, sm = shape
+    n = peek_cases.envs_of(shape)
+    b = adversarial_boards(n, R, C, k, sm, 11, mode)
+    words = batch_rng_words(range(300, 300 + n))
+    s0 = L.emu_spills()
+    got = emu.peek(L, R, C, k, sm, b, words, None, trust_eff=0)
+    assert_peek_equal(got, oracle_peek(b, words, k, sm), f"{shape} {mode}")
+    assert L.emu_status() == 0
+    if (R, C) in ((20, 20), (10, 10)) and mode != "stripes":
+        assert L.emu_spills() > s0, "the adversarial boards were meant to outgrow the LDS lists"
+    if mode == "combo_grid":
+        assert (got["flags"] & peek_cases.FLAG_COMBO).any()
+
+
+# Every instantiation peek_ladder (csrc/tmg_dispatch.h) names, written out by
+# hand from that file: <MAXN, GEN, NB, CODD>, generic ones only
+ALL_PEEKS = {
+    # lean: no bitboards (C = 64), NB x CODD, 512 cells
+    (128, 0, 0, 0),
+    (128, 0, 1, 0), (128, 0, 2, 0), (128, 0, 3, 0), (128, 0, 4, 0),
+    (128, 0, 1, 1), (128, 0, 2, 1), (128, 0, 3, 1), (128, 0, 4, 1),
+    (512, 0, 0, 0),
+    # general: the same
+    (128, 1, 0, 0),
+    (128, 1, 1, 0), (128, 1, 2, 0), (128, 1, 3, 0), (128, 1, 4, 0),
+    (128, 1, 1, 1), (128, 1, 2, 1), (128, 1, 3, 1), (128, 1, 4, 1),
+    (512, 1, 0, 0),
+}
+# (R, C, k, smask), trust_eff -> <MAXN, GEN, NB, CODD>
+PEEK_ROUTES = [
+    ((10, 10, 4, 0), 1, (128, 0, 2, 0)),
+    ((10, 10, 4, 0), 0, (128, 1, 2, 0)),          # an untrusted mask: the general kernel
+    ((10, 10, 4, 14), 1, (128, 1, 2, 0)),         # no shape-specialised peek kernels
+    ((20, 20, 6, 15), 1, (512, 1, 0, 0)),
+    ((20, 20, 6, 0), 1, (512, 0, 0, 0)),
+    ((20, 20, 6, 0), 0, (512, 1, 0, 0)),
+    ((7, 9, 10, 15), 1, (128, 1, 4, 1)),
+    ((2, 64, 4, 0), 1, (128, 0, 0, 0)),
+    ((3, 5, 2, 0), 1, (128, 0, 1, 1)),
+]
+
+
+def test_peek_census(emu_lib):
+    """The route of a few shapes, and: the shapes of test_peek_vs_oracle
+    (trusted) and the crafted shapes (untrusted) reach every instantiation."""
+    emu, L = emu_lib
+    for shape, trust, want in PEEK_ROUTES:
+        got = emu.peek_route(L, *shape, trust_eff=trust)
+        assert tuple(got[f] for f in emu.PEEK_ROUTE) == want, (shape, trust)
+    assert len(ALL_PEEKS) == 20
+    seen = set()
+    for shape, trust in [(s, 1) for s in peek_cases.SHAPES] + [(s, 0) for s in dispatch_cases.CRAFTED_SHAPES]:
+        got = emu.peek_route(L, *shape, trust_eff=trust)
+        seen.add(tuple(got[f] for f in emu.PEEK_ROUTE))
+    assert seen == ALL_PEEKS, f"never launched: {sorted(ALL_PEEKS - seen)}, not in the ladder: {sorted(seen - ALL_PEEKS)}"

@@ -48,6 +48,20 @@ constexpr int kGen128Waves = 5;      // step_kernel<128, true>: c3 (96 VGPRs; 6 
 #endif
 constexpr int kReset512Waves = TMG_RESET512_WAVES;   // reset_kernel<512>: c5's regeneration (7: 0.8 % slower, profiles/r04/s7)
 constexpr int kReset128Waves = TMG_RESET128_WAVES;   // reset_kernel<128> specialised for 10x10 k4 (c3): 63 VGPRs
+// tmg_peek's kernels (tmg_peek.hip).  Lean: 7 / 6 / 5 waves per SIMD measured 4.22 / 4.03 /
+// 3.87 ms per c2 launch (132 B of scratch at 7); general: 5 / 4 / 3 measured 50.6 / 51.8 / 61.0 ms at c3.
+#ifndef TMG_PEEK_LEAN_WAVES
+#define TMG_PEEK_LEAN_WAVES 5
+#endif
+#ifndef TMG_PEEK_GEN_WAVES
+#define TMG_PEEK_GEN_WAVES 5
+#endif
+constexpr int kPeekLean128Waves = TMG_PEEK_LEAN_WAVES;   // peek_kernel<128, false>
+constexpr int kPeekGen128Waves = TMG_PEEK_GEN_WAVES;     // peek_kernel<128, true>
+#ifndef TMG_PEEK_512_WAVES
+#define TMG_PEEK_512_WAVES 1
+#endif
+constexpr int kPeek512Waves = TMG_PEEK_512_WAVES;        // peek_kernel<512, *>
 constexpr int kC5StepWaves = 4;      // step_kernel<512, true> specialised for c5 (128 VGPRs; 3 measured the same)
 
 // compiler-only ordering point between a wave's LDS loads and later stores
@@ -131,6 +145,9 @@ enum : int {
     CV_LANE_REJECT_REDRAW,   // lane kernel: Lemire rejection in a redraw_rows draw
     CV_RP_CARRY,         // rp_take: iteration served from a batch an earlier iteration drew from
     CV_RP_REBATCH,       // rp_take: a second batch within one move
+    CV_PEEK_MOVE,        // tmg_peek (tmg_peek.hip): an action simulated
+    CV_PEEK_SPILL,       // tmg_peek: env queued for peek_spill_kernel
+    CV_PEEK_SPILL_RUN,   // tmg_peek: env re-run by peek_spill_kernel
     CV_COUNT = 40
 };
 #if TMG_COVER
@@ -3062,5 +3079,7 @@ __global__ __launch_bounds__(64) void effective_kernel(Params P, int64_t n, cons
     WSYNC();
     for (int i = lane; i < P.W; i += 64) eff[e * P.W + i] = w.effw[i];
 }
+
+#include "tmg_peek.hip"
 
 }  // namespace tmg

@@ -477,6 +477,33 @@ int tmg_step_onehot(tmg_ctx *ctx, int64_t n, int8_t *board, uint64_t *rng, int32
     return do_step(ctx, P, a, reinterpret_cast<hipStream_t>(stream));
 }
 
+int tmg_peek(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, const uint64_t *eff, int trust_eff,
+             int32_t *reward, int32_t *n_new, int32_t *n_act, uint8_t *flags, int32_t *best_action,
+             int32_t *best_reward, void *stream) {
+    int rc = check_full(ctx, n);
+    if (rc || n == 0) return rc;
+    if (!board || !rng) return fail(-1, "null state buffer");
+    if (trust_eff && !eff) return fail(-1, "trust_eff != 0 needs the effective-action mask");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Params P = ctx->P;
+    // the route rule of a step: lean kernels for a trusted mask with no special
+    // enabled, else the general ones with the spill pass behind them
+    const bool lean = tmg::lean_step(P, trust_eff);
+    if (!lean) {
+        rc = spill_for(ctx, s, n, &P.spill, &P.spill_ws);
+        if (rc) return rc;
+    }
+    const tmg::PeekArgs a{n, board, rng, eff, trust_eff ? 1 : 0, reward, n_new, n_act, flags, best_action, best_reward};
+    const dim3 grid = tmg::env_grid(n);
+    if (lean) tmg::launch_peek_lean(ctx->maxn, ctx->sb, grid, s, P, a);
+    else tmg::launch_peek_gen(ctx->maxn, ctx->sb, grid, s, P, a);
+    rc = hip_check(hipGetLastError(), "kernel launch");
+    if (rc || lean) return rc;
+    if (ctx->maxn == 128) tmg::launch_peek_spill128(s, P, a);       // re-run the envs that ran out of LDS list space
+    else tmg::launch_peek_spill512(s, P, a);
+    return hip_check(hipGetLastError(), "kernel launch");
+}
+
 // ------------------------------------------------------------- step plans
 struct tmg_plan {
     tmg_ctx *ctx;
@@ -770,7 +797,7 @@ __attribute__((visibility("default"))) int tmg_debug_cover(tmg_ctx *ctx, uint64_
 int tmg_num_actions(const tmg_ctx *ctx) { return ctx ? ctx->P.A : -1; }
 int tmg_mask_words(const tmg_ctx *ctx) { return ctx ? ctx->P.W : -1; }
 const char *tmg_last_error(void) { return g_err.c_str(); }
-int tmg_abi_version(void) { return 4; }
+int tmg_abi_version(void) { return 5; }
 const char *tmg_build_info(void) { return "src=" TMG_SRC_SHA ";variant=" TMG_VARIANT; }
 
 }  // extern "C"

@@ -207,6 +207,31 @@ void reset512_ladder(const Params &P, L &l) {
     }
 }
 
+// tmg_peek (tmg_peek.hip): the route rule of a step (lean_step, shape_sb,
+// shape_maxn, sb_planes, C odd), generic instantiations only, in two launcher
+// groups: the lean kernels, and the general ones with the spill tier behind.
+// peek<MAXN, GEN, NB, CODD>()
+template <bool GEN, bool CODD, class L>
+void peek_sb_ladder(const Params &P, L &l) {
+    switch (sb_planes(P.k)) {
+    case 1: l.template peek<128, GEN, 1, CODD>(); break;
+    case 2: l.template peek<128, GEN, 2, CODD>(); break;
+    case 3: l.template peek<128, GEN, 3, CODD>(); break;
+    default: l.template peek<128, GEN, 4, CODD>(); break;
+    }
+}
+template <bool GEN, class L>
+void peek_group_ladder(const Params &P, int maxn, bool sb, L &l) {
+    if (maxn != 128) l.template peek<512, GEN, 0, false>();
+    else if (!sb) l.template peek<128, GEN, 0, false>();
+    else if (P.C & 1) peek_sb_ladder<GEN, true>(P, l);
+    else peek_sb_ladder<GEN, false>(P, l);
+}
+template <class L>
+void peek_lean_ladder(const Params &P, int maxn, bool sb, L &l) { peek_group_ladder<false>(P, maxn, sb, l); }
+template <class L>
+void peek_gen_ladder(const Params &P, int maxn, bool sb, L &l) { peek_group_ladder<true>(P, maxn, sb, l); }
+
 template <class L>
 void effective128_ladder(L &l) { l.template effective<128>(); }
 template <class L>
@@ -227,6 +252,12 @@ template <class L>
 void reset_ladder(const Params &P, int maxn, bool sb, L &l) {
     if (maxn == 128) reset128_ladder(P, sb, l);
     else reset512_ladder(P, l);
+}
+// lean: lean_step(P, trust_eff); the general kernels are followed by the peek spill pass
+template <class L>
+void peek_ladder(const Params &P, int maxn, bool sb, bool lean, L &l) {
+    if (lean) peek_lean_ladder(P, maxn, sb, l);
+    else peek_gen_ladder(P, maxn, sb, l);
 }
 template <class L>
 void effective_ladder(int maxn, L &l) {

@@ -1,5 +1,5 @@
 // tmg_kernels.hip — kernel instantiations and their host launchers
-// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..7, so the
+// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..9, so the
 // heavy template instantiations build in parallel; each TU registers only its
 // own kernels.
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@
 #endif
 
 #ifndef TMG_TU
-#error "compile tmg_kernels.hip with -DTMG_TU=1..7"
+#error "compile tmg_kernels.hip with -DTMG_TU=1..9"
 #endif
 
 namespace tmg {
@@ -84,7 +84,43 @@ struct EffectiveLaunch {
     }
 };
 
+struct PeekLaunch {
+    dim3 grid;
+    hipStream_t s;
+    const Params &P;
+    const PeekArgs &a;
+    template <int MAXN, bool GEN, int NB, bool CODD>
+    void peek() {
+        const size_t lds = sizeof(Ws<MAXN, GEN>);
+        hipLaunchKernelGGL((peek_kernel<MAXN, GEN, NB, CODD>), grid, dim3(64), lds, s, P, a.n, a.board, a.rng, a.eff,
+                           a.trust_eff, a.reward, a.n_new, a.n_act, a.flags, a.best_action, a.best_reward);
+    }
+};
+
+template <int MAXN>
+void peek_spill_one(hipStream_t s, const Params &P, const PeekArgs &a) {
+    const size_t lds = sizeof(Ws<MAXN, false>);
+    hipLaunchKernelGGL((peek_spill_kernel<MAXN>), dim3(kSpillWaves), dim3(64), lds, s, P, a.n, a.board, a.rng, a.eff,
+                       a.trust_eff, a.reward, a.n_new, a.n_act, a.flags, a.best_action, a.best_reward);
+}
+
 }  // namespace
+
+#if TMG_TU == 8
+void launch_peek_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PeekArgs &a) {
+    PeekLaunch l{grid, s, P, a};
+    peek_lean_ladder(P, maxn, sb, l);
+}
+void launch_peek_spill128(hipStream_t s, const Params &P, const PeekArgs &a) { peek_spill_one<128>(s, P, a); }
+void launch_peek_spill512(hipStream_t s, const Params &P, const PeekArgs &a) { peek_spill_one<512>(s, P, a); }
+#endif
+
+#if TMG_TU == 9
+void launch_peek_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PeekArgs &a) {
+    PeekLaunch l{grid, s, P, a};
+    peek_gen_ladder(P, maxn, sb, l);
+}
+#endif
 
 #if TMG_TU == 1
 // The lane-per-board lean step (tmg_lane.h): EPW envs per one-wave

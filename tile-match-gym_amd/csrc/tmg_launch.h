@@ -59,6 +59,24 @@ void launch_sample_effective(hipStream_t s, int64_t n, int W, int A, const uint6
 void launch_count_states(int R, int C, int k, uint64_t total, uint64_t per, uint64_t threads,
                          unsigned long long *counts);
 
+// tmg_peek (tmg_peek.hip): every action's outcome, no state written
+struct PeekArgs {
+    int64_t n;
+    const int8_t *board;
+    const uint64_t *rng;
+    const uint64_t *eff;
+    int trust_eff;
+    int32_t *reward, *n_new, *n_act;
+    uint8_t *flags;
+    int32_t *best_action, *best_reward;
+};
+// TU 8 — lean peek kernels (both families), and the peek spill tier
+void launch_peek_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PeekArgs &a);
+void launch_peek_spill128(hipStream_t s, const Params &P, const PeekArgs &a);
+void launch_peek_spill512(hipStream_t s, const Params &P, const PeekArgs &a);
+// TU 9 — general peek kernels (both families)
+void launch_peek_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PeekArgs &a);
+
 // bytes of one spill-kernel wave's worst-case global-memory lists
 size_t spill_ws_bytes(int maxn);
 

@@ -26,9 +26,9 @@ EXPORTS = ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_ste
            "tmg_onehot", "tmg_onehot_channels", "tmg_count_states", "tmg_sample_effective", "tmg_status",
            "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot", "tmg_plan_create", "tmg_plan_config",
            "tmg_plan_step", "tmg_plan_join", "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch",
-           "tmg_graph_destroy")
+           "tmg_graph_destroy", "tmg_peek")
 DTYPE_F32, DTYPE_U8, DTYPE_I32 = 0, 1, 2
-ABI_VERSION = 4
+ABI_VERSION = 5
 STATUS_INTERNAL, STATUS_OVERFLOW, STATUS_CALLER = 1, 2, 4
 
 # CV_* branch counters of TMG_COVER builds (tmg_board.hip), in index order
@@ -37,7 +37,7 @@ COVER_NAMES = ("sb_lean", "sb_normal", "sb_laser", "sb_perp_bomb", "sb_row_bomb"
                "combo", "spill", "spill_run", "shuffle", "reject", "fast", "shuffle_gen", "reject_gen",
                "rp_passes", "rp_perp", "rp_vlong", "rp_wide", "rp_reject",
                "lane_step", "lane_shuffle", "lane_redraw", "lane_reject", "lane_reject_redraw",
-               "rp_carry", "rp_rebatch")
+               "rp_carry", "rp_rebatch", "peek_move", "peek_spill", "peek_spill_run")
 
 SPECIAL_BITS = {"cookie": 1, "vertical_laser": 2, "horizontal_laser": 4, "bomb": 8}
 FLAG_DONE, FLAG_COMBO, FLAG_SHUFFLED, FLAG_RESET, FLAG_OVERFLOW, FLAG_ERROR = 1, 2, 4, 8, 0x40, 0x80
@@ -96,11 +96,12 @@ def load(path: str = None):
     L.tmg_plan_capture.argtypes = [P, I, P, P, I, P, ctypes.POINTER(P)]
     L.tmg_graph_launch.argtypes = [P, P]
     L.tmg_graph_destroy.argtypes = [P]
+    L.tmg_peek.argtypes = [P, I64, P, P, P, I, P, P, P, P, P, P, P]
     for name in ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_step", "tmg_effective",
                  "tmg_num_actions", "tmg_mask_words", "tmg_abi_version", "tmg_onehot", "tmg_onehot_channels",
                  "tmg_sample_effective", "tmg_status", "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot",
                  "tmg_count_states", "tmg_plan_create", "tmg_plan_config", "tmg_plan_step", "tmg_plan_join",
-                 "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy"):
+                 "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy", "tmg_peek"):
         getattr(L, name).restype = I
     if L.tmg_abi_version() != ABI_VERSION:
         raise TmgError("libtmg.so ABI version mismatch; rebuild it")
@@ -197,6 +198,11 @@ class Context:
         else:
             self._check(self._L.tmg_step(self._h, int(n), board, rng, timer, actions, reward, n_new, n_act, flags, eff,
                                   int(trust_eff), int(autoreset), stream))
+
+    def peek(self, n, board, rng, eff, trust_eff, reward, n_new, n_act, flags, best_action, best_reward, stream):
+        """tmg_peek: every action's step outcome, [n][A] per output (any of them None), no state written."""
+        self._check(self._L.tmg_peek(self._h, int(n), board, rng, eff, int(trust_eff), reward, n_new, n_act, flags,
+                                     best_action, best_reward, stream))
 
     def status(self, clear: bool = False) -> int:
         """Sticky STATUS_* bits of this context (waits for the device)."""

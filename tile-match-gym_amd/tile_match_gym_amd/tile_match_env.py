@@ -374,6 +374,23 @@ class TileMatchEnv(_EnvBase):
         next_obs = self._get_obs()
         return next_obs, num_eliminations, done, False, info
 
+    def peek(self) -> dict:
+        """What step(a) would return for every action a, without changing the
+        env (tmg_peek on the host-side board, untrusted mask, the env's own RNG
+        stream): numpy arrays of shape (A,): reward, num_new_specials,
+        num_specials_activated (int32), is_combination_match, shuffled (bool)."""
+        self._upload()
+        A = self.num_actions
+        out = torch.zeros((3, A), dtype=torch.int32, device=self.device)
+        flags = torch.zeros(A, dtype=torch.uint8, device=self.device)
+        self._ctx.peek(1, self._d_board.data_ptr(), self._d_rng.data_ptr(), None, 0, out[0].data_ptr(),
+                       out[1].data_ptr(), out[2].data_ptr(), flags.data_ptr(), None, None, self._stream())
+        o, f = out.cpu().numpy(), flags.cpu().numpy()
+        if (f & (_native.FLAG_ERROR | _native.FLAG_OVERFLOW)).any():
+            raise _native.TmgError("device reported an error for a peeked move")
+        return {"reward": o[0], "num_new_specials": o[1], "num_specials_activated": o[2],
+                "is_combination_match": (f & _native.FLAG_COMBO) != 0, "shuffled": (f & _native.FLAG_SHUFFLED) != 0}
+
     def _get_obs(self):                                                       # tile_match_env.py:114-115
         return OrderedDict([("board", self.board.board.copy()), ("num_moves_left", self.num_moves - self.timer)])
 

@@ -101,6 +101,7 @@ class TileMatchVecEnv:
         self.n_act = torch.zeros(N, dtype=torch.int32, **kw)
         self.flags = torch.zeros(N, dtype=torch.uint8, **kw)
         self.actions = None                     # step_effective's sampled actions (N,) int32
+        self._peek_bufs = {}                    # peek's output tensors, allocated on first use
         self.onehot = None                      # fused one-hot planes (attach_onehot)
         self._oh_code = _native.DTYPE_F32
         self._eff_valid = False
@@ -310,6 +311,54 @@ class TileMatchVecEnv:
             self._configure()
         self._plans[True].step(self.actions.data_ptr(), int(t), trust, self._stream(), int(fork))
         self._eff_valid = True
+
+    _PEEK_OUTPUTS = {"reward": torch.int32, "n_new": torch.int32, "n_act": torch.int32, "flags": torch.uint8}
+
+    def peek(self, rng=None, outputs=("reward",), best: bool = False) -> dict:
+        """What a step with each action would report, for all A actions of every
+        env at once, without changing any state (tmg_peek): Board.move on a copy
+        of each board.  outputs: any of "reward", "n_new", "n_act" ((N, A)
+        int32) and "flags" ((N, A) uint8: FLAG_COMBO | FLAG_SHUFFLED |
+        FLAG_ERROR); best=True adds "best_action" / "best_reward" ((N,) int32:
+        the lowest action of maximal reward).  Ineffective actions give zeros.
+        rng=None simulates with the envs' own RNG streams, i.e. exactly what the
+        next step will return; an (N, 5) int64 device tensor of other PCG64
+        words gives a sampled lookahead that does not see the env's real
+        refills.  Joins, then enqueues on the current stream; the returned
+        tensors are reused by the next call."""
+        self.join()
+        for name in outputs:
+            if name not in self._PEEK_OUTPUTS:
+                raise ValueError(f"unknown peek output {name!r}")
+        if rng is None:
+            rng = self.rng
+        elif rng.shape != (self.num_envs, 5) or rng.dtype != torch.int64 or rng.device != self.board.device \
+                or not rng.is_contiguous():
+            raise ValueError(f"rng must be a contiguous ({self.num_envs}, 5) int64 tensor on {self.board.device}")
+        bufs = self._peek_bufs
+        names = list(outputs) + (["best_action", "best_reward"] if best else [])
+        for name in names:
+            if name not in bufs:
+                shape = (self.num_envs, self.num_actions) if name in self._PEEK_OUTPUTS else (self.num_envs,)
+                bufs[name] = torch.zeros(shape, dtype=self._PEEK_OUTPUTS.get(name, torch.int32), device=self.device)
+        p = {name: _ptr(bufs[name]) if name in names else None
+             for name in ("reward", "n_new", "n_act", "flags", "best_action", "best_reward")}
+        self.ctx.peek(self.num_envs, _ptr(self.board), _ptr(rng), _ptr(self.eff), int(self._eff_valid), p["reward"],
+                      p["n_new"], p["n_act"], p["flags"], p["best_action"], p["best_reward"], self._stream())
+        return {name: bufs[name] for name in names}
+
+    def step_greedy(self, rng=None, fork: bool = True):
+        """Enqueue one step of the greedy policy: every env takes its lowest
+        action of maximal one-ply reward (peek(best=True) into self.actions; an
+        env with no effective action takes action 0).  rng as for peek: None
+        is the oracle-greedy policy, other words the fair sampled one.  Returns
+        the peeked best reward (N,) int32."""
+        out = self.peek(rng=rng, outputs=(), best=True)
+        if self.actions is None:
+            self.actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.actions.copy_(out["best_action"])
+        self.step_raw(self.actions, fork=fork)
+        return out["best_reward"]
 
     def capture_steps(self, actions=None, ts=None, policy: bool = False, key: int = 12345, first_env: int = 0):
         """Capture len(ts) batched steps into a HIP graph (tmg_plan_capture):

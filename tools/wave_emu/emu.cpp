@@ -276,6 +276,22 @@ struct EmuEffective {
     }
 };
 
+struct EmuPeek {
+    const tmg::Params &P;
+    int64_t n;
+    const int8_t *board; const uint64_t *rng; const uint64_t *eff;
+    int trust_eff;
+    int32_t *reward, *n_new, *n_act; uint8_t *flags; int32_t *best_action, *best_reward;
+    template <int MAXN, bool GEN, int NB, bool CODD>
+    void peek() {
+        run_blocks(n, sizeof(tmg::Ws<MAXN, GEN>), [&] { tmg::peek_kernel<MAXN, GEN, NB, CODD>(P, n, board, rng, eff, trust_eff, reward, n_new, n_act, flags, best_action, best_reward); });
+    }
+    template <int MAXN>
+    void spill() {
+        run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<MAXN, false>), [&] { tmg::peek_spill_kernel<MAXN>(P, n, board, rng, eff, trust_eff, reward, n_new, n_act, flags, best_action, best_reward); });
+    }
+};
+
 static void emu_do_reset(const tmg::Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer, uint64_t *eff,
                          const uint8_t *mask, int bits, int epw) {
     EmuReset l{P, n, board, rng, timer, eff, mask, bits, epw};
@@ -289,6 +305,8 @@ struct Recorder {
     void step() { out[0] = MAXN; out[1] = GEN; out[2] = NB; out[3] = CODD; out[4] = FIX; }
     template <int MAXN, int NB, bool CODD, int FIX>
     void reset() { out[0] = MAXN; out[1] = NB; out[2] = CODD; out[3] = FIX; }
+    template <int MAXN, bool GEN, int NB, bool CODD>
+    void peek() { out[0] = MAXN; out[1] = GEN; out[2] = NB; out[3] = CODD; }
 };
 
 extern "C" {
@@ -353,6 +371,34 @@ int emu_route(int R, int C, int k, int smask, int trust_eff, int mode, int64_t n
     tmg::reset_ladder(P, maxn, sb, rr);
     reset[4] = tmg::reset_envs_per_wave(maxn, false);
     reset[5] = tmg::reset_envs_per_wave(maxn, true);
+    return 0;
+}
+
+// tmg_peek without the stream: peek_ladder, then (general kernels) the peek
+// spill pass.  eff may be NULL when trust_eff == 0; any output may be NULL.
+int emu_peek(int R, int C, int k, int smask, int64_t n, const int8_t *board, const uint64_t *rng, const uint64_t *eff,
+             int trust_eff, int32_t *reward, int32_t *n_new, int32_t *n_act, uint8_t *flags, int32_t *best_action,
+             int32_t *best_reward) {
+    if (!g_jump_init) { tmg::build_jump_table(g_jump); g_jump_init = true; }
+    tmg::Params P = make_params(R, C, k, smask, 1, g_jump);
+    P.spill = spill_queue(g_spill_buf, n);
+    const int maxn = tmg::shape_maxn(P);
+    const bool lean = tmg::lean_step(P, trust_eff);
+    EmuPeek S{P, n, board, rng, eff, trust_eff, reward, n_new, n_act, flags, best_action, best_reward};
+    tmg::peek_ladder(P, maxn, tmg::shape_sb(P), lean, S);
+    if (!lean) {
+        if (maxn == 128) S.spill<128>();
+        else S.spill<512>();
+    }
+    g_spill_total += P.spill->total;
+    return 0;
+}
+
+// out[4]: MAXN, GEN, NB, CODD of the peek kernel the rule picks, nothing run
+int emu_peek_route(int R, int C, int k, int smask, int trust_eff, int *out) {
+    const tmg::Params P = tmg::make_params(R, C, k, smask, 1, nullptr);
+    Recorder r{out};
+    tmg::peek_ladder(P, tmg::shape_maxn(P), tmg::shape_sb(P), tmg::lean_step(P, trust_eff), r);
     return 0;
 }
 

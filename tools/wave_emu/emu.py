@@ -28,6 +28,8 @@ def load(asan=False):
     L.emu_cover.argtypes = [P, I]
     L.emu_cover.restype = None
     L.emu_route.argtypes = [I, I, I, I, I, I, I64, I, I, I, P, P]
+    L.emu_peek.argtypes = [I, I, I, I, I64, P, P, P, I, P, P, P, P, P, P]
+    L.emu_peek_route.argtypes = [I, I, I, I, I, P]
     return L
 
 
@@ -47,6 +49,36 @@ def route(L, R, C, k, smask, trust_eff=1, mode=1, n=1024, have_lane=False, polic
     L.emu_route(R, C, k, smask, int(trust_eff), int(mode), int(n), int(have_lane), int(policy), bits,
                 step.ctypes.data, reset.ctypes.data)
     return dict(zip(STEP_ROUTE, step.tolist())), dict(zip(RESET_ROUTE, reset.tolist()))
+
+
+PEEK_ROUTE = ("MAXN", "GEN", "NB", "CODD")
+
+
+def peek_route(L, R, C, k, smask, trust_eff=1):
+    """The peek kernel instantiation the rule picks (peek_ladder), keyed by PEEK_ROUTE; nothing is run."""
+    out = np.zeros(len(PEEK_ROUTE), np.int32)
+    L.emu_peek_route(R, C, k, smask, int(trust_eff), out.ctypes.data)
+    return dict(zip(PEEK_ROUTE, out.tolist()))
+
+
+def peek(L, R, C, k, smask, board, rng, eff=None, trust_eff=1):
+    """tmg_peek on the emulated kernels: dict of reward / n_new / n_act (n, A)
+    int32, flags (n, A) uint8, best_action / best_reward (n,) int32.  The
+    inputs are only read; eff may be None when trust_eff == 0."""
+    n = board.shape[0]
+    A = 2 * R * C - R - C
+    board = np.ascontiguousarray(board, dtype=np.int8)
+    rng = np.ascontiguousarray(rng, dtype=np.uint64)
+    if eff is not None:
+        eff = np.ascontiguousarray(eff, dtype=np.uint64)
+    out = {name: np.full((n, A), -1, np.int32) for name in ("reward", "n_new", "n_act")}
+    out["flags"] = np.full((n, A), 0x55, np.uint8)
+    out["best_action"] = np.full(n, -1, np.int32)
+    out["best_reward"] = np.full(n, -1, np.int32)
+    L.emu_peek(R, C, k, smask, n, board.ctypes.data, rng.ctypes.data, eff.ctypes.data if eff is not None else None,
+               int(trust_eff), out["reward"].ctypes.data, out["n_new"].ctypes.data, out["n_act"].ctypes.data,
+               out["flags"].ctypes.data, out["best_action"].ctypes.data, out["best_reward"].ctypes.data)
+    return out
 
 
 def cover(L, clear=False):

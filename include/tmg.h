@@ -141,6 +141,51 @@ TMG_API int tmg_peek(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_
                      int32_t *best_reward,  /* [n] that reward                     or NULL */
                      void *stream);
 
+/* Policy rollouts of every action, without changing any state: the simulation
+ * step of a Monte-Carlo planner.  Rollout (s, i, a), for every sample s in
+ * [0, samples), env i and action a in [0, A):
+ *   State: a copy of board[i] and of the RNG words rng[s][i].
+ *   An action that is not effective on the board as it stands: ret = plies =
+ *     flags = 0 (trust_eff as tmg_peek: non-zero, eff is this library's mask
+ *     and the lean kernels run when no special is enabled; zero, eff may be
+ *     NULL, the mask is scanned and hand-edited boards work).
+ *   Horizon: H = depth when timer is NULL, else min(depth, num_moves -
+ *     timer[i]) (the episode ends when the timer reaches num_moves).  H <= 0,
+ *     a finished env: zeros for every action of that env.
+ *   Ply 0 is Board.move(a) (board.py:330-395).  Ply d, 1 <= d < H, plays the
+ *     action tmg_sample_effective would draw for that env from the mask of the
+ *     board as ply d - 1 left it, with key (key + s * A + a) mod 2^64, global
+ *     env first_env + i and step counter t + d (src/examples/q_learning.py:
+ *     19-25: uniform over the effective actions).  The RNG stream runs on from
+ *     ply to ply.
+ *   ret: the sum of the plies' num_eliminations; plies: how many were played;
+ *     flags: the OR of the plies' TMG_FLAG_COMBO | TMG_FLAG_SHUFFLED.  A ply
+ *     that ends on a safety cap sets TMG_FLAG_ERROR, stops that rollout and
+ *     raises TMG_STATUS_INTERNAL; a lean launch that meets a non-normal tile
+ *     flags every action of that (s, i), as tmg_peek does.
+ *   total[i][a] = sum over s of ret[s][i][a]; best_action[i]: the lowest a of
+ *     maximal total over all A actions (0 when none is effective);
+ *     best_total[i]: that total.  These three need ret.
+ *   With depth == 1 and samples == 1, ret / flags are tmg_peek's reward /
+ *     flags for the same rng.
+ *   depth >= 1, samples >= 1, n * samples <= 2^26 - 8 (one wave each).  n == 0
+ *     is a no-op; a tmg_create_scan context refuses the call.  Nothing of
+ *     board, rng, timer, eff is written.  A (sample, env) one of whose plies
+ *     outgrew the kernels' LDS lists is re-run whole on the worst-case lists
+ *     and counts in tmg_spills. */
+TMG_API int tmg_rollout(tmg_ctx *ctx, int64_t n, const int8_t *board,
+                        const uint64_t *rng,      /* [samples][n][5], only read */
+                        const int32_t *timer,     /* [n] or NULL (no horizon) */
+                        const uint64_t *eff, int trust_eff,
+                        int depth, int samples, uint64_t key, int64_t first_env, int32_t t,
+                        int32_t *ret,             /* [samples][n][A] summed num_eliminations, or NULL */
+                        int32_t *plies,           /* [samples][n][A] moves played (0 = not simulated), or NULL */
+                        uint8_t *flags,           /* [samples][n][A] OR of COMBO | SHUFFLED | ERROR, or NULL */
+                        int32_t *total,           /* [n][A] sum over samples of ret, or NULL */
+                        int32_t *best_action,     /* [n] lowest a of maximal total, or NULL */
+                        int32_t *best_total,      /* [n] that total, or NULL */
+                        void *stream);
+
 /* Step plans: one host call per batched step of a fixed set of buffers
  * (TileMatchEnv.step, tile_match_env.py:93-124, for every env of the batch),
  * with the batch split into env groups on their own streams, the callers'

@@ -76,6 +76,38 @@ __global__ __launch_bounds__(BS) void sample_effective_kernel(int64_t n, int W, 
     actions[i] = draw_row(m, W, A, policy_draw(key, (uint64_t)(first_env + i), t));
 }
 
+// tmg_rollout's sums over the samples (launched behind the rollout kernels on
+// their stream): total[e][a] = sum_s ret[s][e][a], and per env the lowest
+// action of maximal total (action 0, total 0 when no action is effective:
+// returns are >= 0).  One wave per env in wg_env's order; lane l takes the
+// actions l, l + 64, ..., so every slice of ret is read and total written in
+// whole coalesced rows; then a wave-wide maximum (wave_max) of the lanes'
+// bests and, among the lanes holding it, of the negated action index.
+// total / best_action / best_total: each may be null.
+__global__ __launch_bounds__(64) void rollout_reduce_kernel(int64_t n, int A, int samples,
+                                                            const int32_t *__restrict__ ret,
+                                                            int32_t *__restrict__ total,
+                                                            int32_t *__restrict__ best_action,
+                                                            int32_t *__restrict__ best_total) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = wg_env();
+    if (e >= n) return;
+    int bv = (int)0x80000000, ba = 0x7fffffff;     // this lane's best: ascending a, so `>` keeps the lowest
+    for (int a = lane; a < A; a += 64) {
+        int sum = 0;
+        for (int s = 0; s < samples; s++) sum += ret[((int64_t)s * n + e) * A + a];
+        if (total) total[e * A + a] = sum;
+        if (sum > bv) { bv = sum; ba = a; }
+    }
+    if (!best_action && !best_total) return;
+    const int mx = wave_max(bv);
+    const int lowest = -wave_max(bv == mx ? -ba : (int)0x80000000);
+    if (lane == 0) {
+        if (best_action) best_action[e] = lowest;
+        if (best_total) best_total[e] = mx;
+    }
+}
+
 // utils.compute_num_states / is_valid_state (src/tile_match_gym/utils/utils.py:6-26):
 // over every colouring of an all-normal R x C board with colours 1..k (the
 // itertools.product order: cell 0 is the most significant digit), count the

@@ -148,7 +148,11 @@ enum : int {
     CV_PEEK_MOVE,        // tmg_peek (tmg_peek.hip): an action simulated
     CV_PEEK_SPILL,       // tmg_peek: env queued for peek_spill_kernel
     CV_PEEK_SPILL_RUN,   // tmg_peek: env re-run by peek_spill_kernel
-    CV_COUNT = 40
+    CV_ROLL_PLY,         // tmg_rollout (tmg_rollout.hip): a continuation ply (d >= 1) played
+    CV_ROLL_HORIZON,     // tmg_rollout: a rollout ended before `depth` because of the timer
+    CV_ROLL_SPILL,       // tmg_rollout: virtual env queued for rollout_spill_kernel
+    CV_ROLL_SPILL_RUN,   // tmg_rollout: virtual env re-run by rollout_spill_kernel
+    CV_COUNT = 48
 };
 #if TMG_COVER
 #define COVER(site)                                                                                     \
@@ -3081,5 +3085,6 @@ __global__ __launch_bounds__(64) void effective_kernel(Params P, int64_t n, cons
 }
 
 #include "tmg_peek.hip"
+#include "tmg_rollout.hip"
 
 }  // namespace tmg

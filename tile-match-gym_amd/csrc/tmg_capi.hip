@@ -504,6 +504,52 @@ int tmg_peek(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, 
     return hip_check(hipGetLastError(), "kernel launch");
 }
 
+int tmg_rollout(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, const int32_t *timer,
+                const uint64_t *eff, int trust_eff, int depth, int samples, uint64_t key, int64_t first_env, int32_t t,
+                int32_t *ret, int32_t *plies, uint8_t *flags, int32_t *total, int32_t *best_action,
+                int32_t *best_total, void *stream) {
+    int rc = check_full(ctx, n);
+    if (rc) return rc;
+    if (depth < 1) return fail(-2, "rollout depth must be >= 1");
+    if (samples < 1) return fail(-2, "rollout samples must be >= 1");
+    if ((total || best_action || best_total) && !ret) return fail(-1, "total / best_action / best_total need ret");
+    // one wave per (sample, env): the padded grid's threads must stay below 2^32
+    constexpr int64_t kMaxWaves = (1LL << 26) - 8;
+    if (n > kMaxWaves / samples) return fail(-2, "n * samples is more than one launch holds (2^26 - 8 waves)");
+    if (first_env < 0) return fail(-2, "first_env must be >= 0");
+    if (n == 0) return 0;
+    if (!board || !rng) return fail(-1, "null state buffer");
+    if (trust_eff && !eff) return fail(-1, "trust_eff != 0 needs the effective-action mask");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int64_t nv = n * samples;
+    Params P = ctx->P;
+    P.pol_key = key;
+    P.pol_first = first_env;
+    P.pol_t = t;
+    // peek's route: lean kernels for a trusted mask with no special enabled,
+    // else the general ones with the spill pass behind them
+    const bool lean = tmg::lean_step(P, trust_eff);
+    if (!lean) {
+        rc = spill_for(ctx, s, nv, &P.spill, &P.spill_ws);
+        if (rc) return rc;
+    }
+    const tmg::RollArgs a{n, samples, depth, board, rng, timer, eff, trust_eff ? 1 : 0, ret, plies, flags};
+    const dim3 grid = tmg::env_grid(nv);
+    if (lean) tmg::launch_rollout_lean(ctx->maxn, ctx->sb, grid, s, P, a);
+    else tmg::launch_rollout_gen(ctx->maxn, ctx->sb, grid, s, P, a);
+    rc = hip_check(hipGetLastError(), "kernel launch");
+    if (rc) return rc;
+    if (!lean) {                                   // re-run the virtual envs that ran out of LDS list space
+        if (ctx->maxn == 128) tmg::launch_rollout_spill128(s, P, a);
+        else tmg::launch_rollout_spill512(s, P, a);
+        rc = hip_check(hipGetLastError(), "kernel launch");
+        if (rc) return rc;
+    }
+    if (!total && !best_action && !best_total) return 0;
+    tmg::launch_rollout_reduce(s, n, P.A, samples, ret, total, best_action, best_total);
+    return hip_check(hipGetLastError(), "kernel launch");
+}
+
 // ------------------------------------------------------------- step plans
 struct tmg_plan {
     tmg_ctx *ctx;
@@ -797,7 +843,7 @@ __attribute__((visibility("default"))) int tmg_debug_cover(tmg_ctx *ctx, uint64_
 int tmg_num_actions(const tmg_ctx *ctx) { return ctx ? ctx->P.A : -1; }
 int tmg_mask_words(const tmg_ctx *ctx) { return ctx ? ctx->P.W : -1; }
 const char *tmg_last_error(void) { return g_err.c_str(); }
-int tmg_abi_version(void) { return 5; }
+int tmg_abi_version(void) { return 6; }
 const char *tmg_build_info(void) { return "src=" TMG_SRC_SHA ";variant=" TMG_VARIANT; }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // tmg_kernels.hip — kernel instantiations and their host launchers
-// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..9, so the
+// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..11, so the
 // heavy template instantiations build in parallel; each TU registers only its
 // own kernels.
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@
 #endif
 
 #ifndef TMG_TU
-#error "compile tmg_kernels.hip with -DTMG_TU=1..9"
+#error "compile tmg_kernels.hip with -DTMG_TU=1..11"
 #endif
 
 namespace tmg {
@@ -104,7 +104,43 @@ void peek_spill_one(hipStream_t s, const Params &P, const PeekArgs &a) {
                        a.trust_eff, a.reward, a.n_new, a.n_act, a.flags, a.best_action, a.best_reward);
 }
 
+// tmg_rollout takes peek's dispatch (peek_ladder): peek<...>() launches the
+// rollout kernel of the same instantiation
+struct RollLaunch {
+    dim3 grid;
+    hipStream_t s;
+    const Params &P;
+    const RollArgs &a;
+    template <int MAXN, bool GEN, int NB, bool CODD>
+    void peek() {
+        const size_t lds = sizeof(Ws<MAXN, GEN>);
+        hipLaunchKernelGGL((rollout_kernel<MAXN, GEN, NB, CODD>), grid, dim3(64), lds, s, P, a);
+    }
+};
+
+template <int MAXN>
+void rollout_spill_one(hipStream_t s, const Params &P, const RollArgs &a) {
+    const size_t lds = sizeof(Ws<MAXN, false>);
+    hipLaunchKernelGGL((rollout_spill_kernel<MAXN>), dim3(kSpillWaves), dim3(64), lds, s, P, a);
+}
+
 }  // namespace
+
+#if TMG_TU == 10
+void launch_rollout_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const RollArgs &a) {
+    RollLaunch l{grid, s, P, a};
+    peek_lean_ladder(P, maxn, sb, l);
+}
+void launch_rollout_spill128(hipStream_t s, const Params &P, const RollArgs &a) { rollout_spill_one<128>(s, P, a); }
+void launch_rollout_spill512(hipStream_t s, const Params &P, const RollArgs &a) { rollout_spill_one<512>(s, P, a); }
+#endif
+
+#if TMG_TU == 11
+void launch_rollout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const RollArgs &a) {
+    RollLaunch l{grid, s, P, a};
+    peek_gen_ladder(P, maxn, sb, l);
+}
+#endif
 
 #if TMG_TU == 8
 void launch_peek_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PeekArgs &a) {
@@ -254,6 +290,11 @@ void launch_count_states(int R, int C, int k, uint64_t total, uint64_t per, uint
     const CountGeo G = make_count_geo(R, C, k);
     hipLaunchKernelGGL(count_states_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, G, total, per,
                        counts);
+}
+void launch_rollout_reduce(hipStream_t s, int64_t n, int A, int samples, const int32_t *ret, int32_t *total,
+                           int32_t *best_action, int32_t *best_total) {
+    hipLaunchKernelGGL(rollout_reduce_kernel, env_grid(n), dim3(64), 0, s, n, A, samples, ret, total, best_action,
+                       best_total);
 }
 #endif
 

@@ -77,6 +77,19 @@ void launch_peek_spill512(hipStream_t s, const Params &P, const PeekArgs &a);
 // TU 9 — general peek kernels (both families)
 void launch_peek_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PeekArgs &a);
 
+// tmg_rollout (tmg_rollout.hip): every action's policy rollout, no state
+// written.  grid: env_grid(n * samples), one wave per virtual env
+struct RollArgs;
+// TU 10 — lean rollout kernels (both families), and the rollout spill tier
+void launch_rollout_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const RollArgs &a);
+void launch_rollout_spill128(hipStream_t s, const Params &P, const RollArgs &a);
+void launch_rollout_spill512(hipStream_t s, const Params &P, const RollArgs &a);
+// TU 11 — general rollout kernels (both families)
+void launch_rollout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const RollArgs &a);
+// TU 6 — the sums over the samples (tmg_aux.hip)
+void launch_rollout_reduce(hipStream_t s, int64_t n, int A, int samples, const int32_t *ret, int32_t *total,
+                           int32_t *best_action, int32_t *best_total);
+
 // bytes of one spill-kernel wave's worst-case global-memory lists
 size_t spill_ws_bytes(int maxn);
 

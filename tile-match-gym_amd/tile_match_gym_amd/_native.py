@@ -26,9 +26,9 @@ EXPORTS = ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_ste
            "tmg_onehot", "tmg_onehot_channels", "tmg_count_states", "tmg_sample_effective", "tmg_status",
            "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot", "tmg_plan_create", "tmg_plan_config",
            "tmg_plan_step", "tmg_plan_join", "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch",
-           "tmg_graph_destroy", "tmg_peek")
+           "tmg_graph_destroy", "tmg_peek", "tmg_rollout")
 DTYPE_F32, DTYPE_U8, DTYPE_I32 = 0, 1, 2
-ABI_VERSION = 5
+ABI_VERSION = 6
 STATUS_INTERNAL, STATUS_OVERFLOW, STATUS_CALLER = 1, 2, 4
 
 # CV_* branch counters of TMG_COVER builds (tmg_board.hip), in index order
@@ -37,7 +37,8 @@ COVER_NAMES = ("sb_lean", "sb_normal", "sb_laser", "sb_perp_bomb", "sb_row_bomb"
                "combo", "spill", "spill_run", "shuffle", "reject", "fast", "shuffle_gen", "reject_gen",
                "rp_passes", "rp_perp", "rp_vlong", "rp_wide", "rp_reject",
                "lane_step", "lane_shuffle", "lane_redraw", "lane_reject", "lane_reject_redraw",
-               "rp_carry", "rp_rebatch", "peek_move", "peek_spill", "peek_spill_run")
+               "rp_carry", "rp_rebatch", "peek_move", "peek_spill", "peek_spill_run",
+               "roll_ply", "roll_horizon", "roll_spill", "roll_spill_run")
 
 SPECIAL_BITS = {"cookie": 1, "vertical_laser": 2, "horizontal_laser": 4, "bomb": 8}
 FLAG_DONE, FLAG_COMBO, FLAG_SHUFFLED, FLAG_RESET, FLAG_OVERFLOW, FLAG_ERROR = 1, 2, 4, 8, 0x40, 0x80
@@ -97,11 +98,13 @@ def load(path: str = None):
     L.tmg_graph_launch.argtypes = [P, P]
     L.tmg_graph_destroy.argtypes = [P]
     L.tmg_peek.argtypes = [P, I64, P, P, P, I, P, P, P, P, P, P, P]
+    L.tmg_rollout.argtypes = [P, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32, P, P, P, P, P, P, P]
     for name in ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_step", "tmg_effective",
                  "tmg_num_actions", "tmg_mask_words", "tmg_abi_version", "tmg_onehot", "tmg_onehot_channels",
                  "tmg_sample_effective", "tmg_status", "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot",
                  "tmg_count_states", "tmg_plan_create", "tmg_plan_config", "tmg_plan_step", "tmg_plan_join",
-                 "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy", "tmg_peek"):
+                 "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy", "tmg_peek",
+                 "tmg_rollout"):
         getattr(L, name).restype = I
     if L.tmg_abi_version() != ABI_VERSION:
         raise TmgError("libtmg.so ABI version mismatch; rebuild it")
@@ -203,6 +206,14 @@ class Context:
         """tmg_peek: every action's step outcome, [n][A] per output (any of them None), no state written."""
         self._check(self._L.tmg_peek(self._h, int(n), board, rng, eff, int(trust_eff), reward, n_new, n_act, flags,
                                      best_action, best_reward, stream))
+
+    def rollout(self, n, board, rng, timer, eff, trust_eff, depth, samples, key, first_env, t, ret, plies, flags,
+                total, best_action, best_total, stream):
+        """tmg_rollout: every action's policy rollout, [samples][n][A] per rollout output, [n][A] / [n] for the
+        sums over samples (any of them None; the sums need ret), no state written.  timer None: no horizon."""
+        self._check(self._L.tmg_rollout(self._h, int(n), board, rng, timer, eff, int(trust_eff), int(depth),
+                                        int(samples), int(key) % 2 ** 64, int(first_env), int(t), ret, plies, flags,
+                                        total, best_action, best_total, stream))
 
     def status(self, clear: bool = False) -> int:
         """Sticky STATUS_* bits of this context (waits for the device)."""

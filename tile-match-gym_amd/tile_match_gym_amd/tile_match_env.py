@@ -391,6 +391,45 @@ class TileMatchEnv(_EnvBase):
         return {"reward": o[0], "num_new_specials": o[1], "num_specials_activated": o[2],
                 "is_combination_match": (f & _native.FLAG_COMBO) != 0, "shuffled": (f & _native.FLAG_SHUFFLED) != 0}
 
+    def rollout(self, depth: int, samples: int = 1, seeds=None, key: int = 12345, t: int = 0) -> dict:
+        """Policy rollouts of every action, without changing the env
+        (tmg_rollout on the host-side board, untrusted mask, the env's timer as
+        the horizon): action a, then the examples' uniform policy over the
+        effective actions for min(depth, moves left) plies in all, drawn with
+        key (key + s * A + a) mod 2^64 and step counter t + d.  seeds: one
+        integer seed per sample for the simulated refills (None, samples == 1
+        only: the env's own RNG stream).  numpy arrays of shape (samples, A):
+        ret (the summed rewards), plies (int32), is_combination_match, shuffled
+        (bool: in any ply)."""
+        from .seeding import batch_rng_words
+        depth, samples = int(depth), int(samples)
+        if depth < 1 or samples < 1:
+            raise ValueError("rollout depth and samples must be >= 1")
+        if self.timer is None:
+            raise Exception("You must call reset before calling rollout")
+        self._upload()
+        if seeds is None:
+            if samples != 1:
+                raise ValueError("seeds=None (the env's own stream) needs samples == 1")
+            rng = self._d_rng
+        else:
+            seeds = list(seeds)
+            if len(seeds) != samples:
+                raise ValueError("one seed per sample")
+            rng = torch.from_numpy(batch_rng_words(seeds).view(np.int64)).to(self.device).reshape(samples, 1, 5)
+        self._d_timer.fill_(self.timer)
+        A = self.num_actions
+        out = torch.zeros((2, samples, A), dtype=torch.int32, device=self.device)
+        flags = torch.zeros((samples, A), dtype=torch.uint8, device=self.device)
+        self._ctx.rollout(1, self._d_board.data_ptr(), rng.data_ptr(), self._d_timer.data_ptr(), None, 0, depth,
+                          samples, key, 0, t, out[0].data_ptr(), out[1].data_ptr(), flags.data_ptr(), None, None, None,
+                          self._stream())
+        o, f = out.cpu().numpy(), flags.cpu().numpy()
+        if (f & (_native.FLAG_ERROR | _native.FLAG_OVERFLOW)).any():
+            raise _native.TmgError("device reported an error for a simulated move")
+        return {"ret": o[0], "plies": o[1], "is_combination_match": (f & _native.FLAG_COMBO) != 0,
+                "shuffled": (f & _native.FLAG_SHUFFLED) != 0}
+
     def _get_obs(self):                                                       # tile_match_env.py:114-115
         return OrderedDict([("board", self.board.board.copy()), ("num_moves_left", self.num_moves - self.timer)])
 

@@ -102,6 +102,7 @@ class TileMatchVecEnv:
         self.flags = torch.zeros(N, dtype=torch.uint8, **kw)
         self.actions = None                     # step_effective's sampled actions (N,) int32
         self._peek_bufs = {}                    # peek's output tensors, allocated on first use
+        self._roll_bufs = {}                    # rollout's, by sample count
         self.onehot = None                      # fused one-hot planes (attach_onehot)
         self._oh_code = _native.DTYPE_F32
         self._eff_valid = False
@@ -359,6 +360,75 @@ class TileMatchVecEnv:
         self.actions.copy_(out["best_action"])
         self.step_raw(self.actions, fork=fork)
         return out["best_reward"]
+
+    _ROLL_OUTPUTS = {"ret": torch.int32, "plies": torch.int32, "flags": torch.uint8, "total": torch.int32}
+
+    def rollout(self, depth: int, samples: int = 1, rng=None, key: int = 12345, first_env: int = 0, t: int = 0,
+                horizon: bool = True, outputs=("ret",), best: bool = False) -> dict:
+        """Policy rollouts of every action of every env, without changing any
+        state (tmg_rollout): rollout (s, i, a) plays action a on a copy of
+        board i with the RNG words rng[s, i], then continues with the examples'
+        policy (uniform over the effective actions: step_effective's draw with
+        key (key + s * A + a) mod 2^64, global env first_env + i and step
+        counter t + d at ply d) for min(depth, moves left) plies in all
+        (horizon=False: depth plies whatever the timer says).  outputs: any of
+        "ret" (the summed rewards), "plies" ((S, N, A) int32), "flags" ((S, N,
+        A) uint8: the OR of the plies' FLAG_COMBO | FLAG_SHUFFLED | FLAG_ERROR)
+        and "total" ((N, A) int32: ret summed over the samples); best=True adds
+        "best_action" / "best_total" ((N,) int32: the lowest action of maximal
+        total).  Ineffective actions and finished envs give zeros.  rng=None
+        (samples == 1 only) simulates with the envs' own RNG streams, i.e. with
+        the refills the env will really draw; otherwise a contiguous (S, N, 5)
+        int64 device tensor of PCG64 words ((N, 5) for S = 1).  Joins, then
+        enqueues on the current stream; the returned tensors are reused by the
+        next call of the same samples."""
+        self.join()
+        depth, samples = int(depth), int(samples)
+        if depth < 1:
+            raise ValueError("rollout depth must be >= 1")
+        if samples < 1:
+            raise ValueError("rollout samples must be >= 1")
+        for name in outputs:
+            if name not in self._ROLL_OUTPUTS:
+                raise ValueError(f"unknown rollout output {name!r}")
+        N, A = self.num_envs, self.num_actions
+        if rng is None:
+            if samples != 1:
+                raise ValueError("rng=None (the envs' own streams) needs samples == 1: pass (S, N, 5) words")
+            rng = self.rng
+        else:
+            ok = (N, 5) if samples == 1 else None
+            if (tuple(rng.shape) != (samples, N, 5) and tuple(rng.shape) != ok) or rng.dtype != torch.int64 \
+                    or rng.device != self.board.device or not rng.is_contiguous():
+                raise ValueError(f"rng must be a contiguous ({samples}, {N}, 5) int64 tensor on {self.board.device}")
+        names = list(outputs) + (["best_action", "best_total"] if best else [])
+        # the sums over the samples are taken from ret
+        need = set(names) | ({"ret"} if best or "total" in names else set())
+        bufs = self._roll_bufs.setdefault(samples, {})
+        for name in need:
+            if name not in bufs:
+                shape = (samples, N, A) if name in ("ret", "plies", "flags") else (N, A) if name == "total" else (N,)
+                bufs[name] = torch.zeros(shape, dtype=self._ROLL_OUTPUTS.get(name, torch.int32), device=self.device)
+        p = {name: _ptr(bufs[name]) if name in need else None
+             for name in ("ret", "plies", "flags", "total", "best_action", "best_total")}
+        self.ctx.rollout(N, _ptr(self.board), _ptr(rng), _ptr(self.timer) if horizon else None, _ptr(self.eff),
+                         int(self._eff_valid), depth, samples, key, first_env, t, p["ret"], p["plies"], p["flags"],
+                         p["total"], p["best_action"], p["best_total"], self._stream())
+        return {name: bufs[name] for name in names}
+
+    def step_rollout_greedy(self, depth: int, samples: int = 1, rng=None, key: int = 12345, first_env: int = 0,
+                            t: int = 0, horizon: bool = True, fork: bool = True):
+        """Enqueue one step of the rollout-greedy policy: every env takes its
+        lowest action of maximal summed rollout return (rollout(best=True) into
+        self.actions; an env with no effective action takes action 0).
+        Arguments as for rollout.  Returns that best total (N,) int32."""
+        out = self.rollout(depth, samples, rng=rng, key=key, first_env=first_env, t=t, horizon=horizon, outputs=(),
+                           best=True)
+        if self.actions is None:
+            self.actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.actions.copy_(out["best_action"])
+        self.step_raw(self.actions, fork=fork)
+        return out["best_total"]
 
     def capture_steps(self, actions=None, ts=None, policy: bool = False, key: int = 12345, first_env: int = 0):
         """Capture len(ts) batched steps into a HIP graph (tmg_plan_capture):

@@ -3,6 +3,7 @@
 // lane, so AddressSanitizer / gdb see every LDS and global index.
 #include "hip/hip_runtime.h"
 #include "tmg_board.hip"
+#include "tmg_aux.hip"
 #include "tmg_dispatch.h"
 
 #include <setjmp.h>
@@ -292,6 +293,20 @@ struct EmuPeek {
     }
 };
 
+// tmg_rollout takes peek's dispatch: peek<...>() runs the rollout kernel
+struct EmuRollout {
+    const tmg::Params &P;
+    const tmg::RollArgs &a;
+    template <int MAXN, bool GEN, int NB, bool CODD>
+    void peek() {
+        run_blocks(a.n * a.samples, sizeof(tmg::Ws<MAXN, GEN>), [&] { tmg::rollout_kernel<MAXN, GEN, NB, CODD>(P, a); });
+    }
+    template <int MAXN>
+    void spill() {
+        run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<MAXN, false>), [&] { tmg::rollout_spill_kernel<MAXN>(P, a); });
+    }
+};
+
 static void emu_do_reset(const tmg::Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer, uint64_t *eff,
                          const uint8_t *mask, int bits, int epw) {
     EmuReset l{P, n, board, rng, timer, eff, mask, bits, epw};
@@ -399,6 +414,36 @@ int emu_peek_route(int R, int C, int k, int smask, int trust_eff, int *out) {
     const tmg::Params P = tmg::make_params(R, C, k, smask, 1, nullptr);
     Recorder r{out};
     tmg::peek_ladder(P, tmg::shape_maxn(P), tmg::shape_sb(P), tmg::lean_step(P, trust_eff), r);
+    return 0;
+}
+
+// tmg_rollout without the stream: peek_ladder on the rollout kernels, then
+// (general kernels) the rollout spill pass, then the reduce kernel when one of
+// total / best_action / best_total is asked for.  eff may be NULL when
+// trust_eff == 0, timer NULL for no horizon; any output may be NULL.
+int emu_rollout(int R, int C, int k, int smask, int moves, int64_t n, const int8_t *board, const uint64_t *rng,
+                const int32_t *timer, const uint64_t *eff, int trust_eff, int depth, int samples, uint64_t key,
+                int64_t first_env, int32_t t, int32_t *ret, int32_t *plies, uint8_t *flags, int32_t *total,
+                int32_t *best_action, int32_t *best_total) {
+    if (!g_jump_init) { tmg::build_jump_table(g_jump); g_jump_init = true; }
+    if (depth < 1 || samples < 1 || ((total || best_action || best_total) && !ret)) return -2;
+    tmg::Params P = make_params(R, C, k, smask, moves, g_jump);
+    P.spill = spill_queue(g_spill_buf, n * samples);
+    P.pol_key = key;
+    P.pol_first = first_env;
+    P.pol_t = t;
+    const int maxn = tmg::shape_maxn(P);
+    const bool lean = tmg::lean_step(P, trust_eff);
+    const tmg::RollArgs a{n, samples, depth, board, rng, timer, eff, trust_eff ? 1 : 0, ret, plies, flags};
+    EmuRollout S{P, a};
+    tmg::peek_ladder(P, maxn, tmg::shape_sb(P), lean, S);
+    if (!lean) {
+        if (maxn == 128) S.spill<128>();
+        else S.spill<512>();
+    }
+    g_spill_total += P.spill->total;
+    if (total || best_action || best_total)
+        run_blocks(n, 0, [&] { tmg::rollout_reduce_kernel(n, P.A, samples, ret, total, best_action, best_total); });
     return 0;
 }
 

@@ -30,6 +30,8 @@ def load(asan=False):
     L.emu_route.argtypes = [I, I, I, I, I, I, I64, I, I, I, P, P]
     L.emu_peek.argtypes = [I, I, I, I, I64, P, P, P, I, P, P, P, P, P, P]
     L.emu_peek_route.argtypes = [I, I, I, I, I, P]
+    L.emu_rollout.argtypes = [I, I, I, I, I, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32,
+                              P, P, P, P, P, P]
     return L
 
 
@@ -78,6 +80,34 @@ def peek(L, R, C, k, smask, board, rng, eff=None, trust_eff=1):
     L.emu_peek(R, C, k, smask, n, board.ctypes.data, rng.ctypes.data, eff.ctypes.data if eff is not None else None,
                int(trust_eff), out["reward"].ctypes.data, out["n_new"].ctypes.data, out["n_act"].ctypes.data,
                out["flags"].ctypes.data, out["best_action"].ctypes.data, out["best_reward"].ctypes.data)
+    return out
+
+
+def rollout(L, R, C, k, smask, num_moves, board, rng, timer, eff, trust_eff, depth, samples, key, first_env, t):
+    """tmg_rollout on the emulated kernels: dict of ret / plies (S, n, A) int32,
+    flags (S, n, A) uint8, total (n, A), best_action / best_total (n,) int32.
+    rng: (S, n, 5) uint64 ((n, 5) for S = 1).  The inputs are only read; timer
+    None is no horizon; eff may be None when trust_eff == 0."""
+    n = board.shape[0]
+    A = 2 * R * C - R - C
+    board = np.ascontiguousarray(board, dtype=np.int8)
+    rng = np.ascontiguousarray(rng, dtype=np.uint64)
+    assert rng.size == samples * n * 5
+    if timer is not None:
+        timer = np.ascontiguousarray(timer, dtype=np.int32)
+    if eff is not None:
+        eff = np.ascontiguousarray(eff, dtype=np.uint64)
+    out = {name: np.full((samples, n, A), -1, np.int32) for name in ("ret", "plies")}
+    out["flags"] = np.full((samples, n, A), 0x55, np.uint8)
+    out["total"] = np.full((n, A), -1, np.int32)
+    out["best_action"] = np.full(n, -1, np.int32)
+    out["best_total"] = np.full(n, -1, np.int32)
+    rc = L.emu_rollout(R, C, k, smask, int(num_moves), n, board.ctypes.data, rng.ctypes.data,
+                       timer.ctypes.data if timer is not None else None, eff.ctypes.data if eff is not None else None,
+                       int(trust_eff), int(depth), int(samples), int(key) % 2 ** 64, int(first_env), int(t),
+                       *(out[f].ctypes.data for f in ("ret", "plies", "flags", "total", "best_action", "best_total")))
+    if rc:
+        raise ValueError(f"emu_rollout refused the call ({rc})")
     return out
 
 

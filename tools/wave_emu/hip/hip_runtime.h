@@ -56,6 +56,7 @@ inline int __ffsll(unsigned long long x) { return __builtin_ffsll((long long)x);
 inline uint64_t __umul64hi(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) >> 64); }
 
 struct alignas(16) uint4 { uint32_t x, y, z, w; };
+struct int4 { int x, y, z, w; };
 inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
 
 inline int min(int a, int b) { return a < b ? a : b; }

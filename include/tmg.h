@@ -302,6 +302,35 @@ TMG_API int tmg_reset_onehot(tmg_ctx *ctx, int64_t n, int8_t *board, uint64_t *r
 TMG_API int tmg_sample_effective(tmg_ctx *ctx, int64_t n, const uint64_t *eff, uint64_t key, int64_t first_env,
                                  int32_t t, int32_t *actions, void *stream);
 
+/* Replaces the per-env np.random.default_rng(...) of TileMatchEnv.__init__ and
+ * set_seed (tile_match_env.py:49, 79-82) for m streams at once, on the device:
+ * rng[j] ([m][5], the layout above, half-word buffer empty) becomes the state
+ * of PCG64(SeedSequence(...)) exactly as numpy seeds it.
+ *   TMG_SEED_INT: row j is np.random.default_rng(seed_j).  seed_j is seeds[j]
+ *     (seed_words == 1) or seeds[2j] | seeds[2j+1] << 64 (seed_words == 2), a
+ *     device array; with seeds == NULL it is base + j, base = base_lo |
+ *     base_hi << 64 (no array at all).  key0, key1 and period are not used.
+ *   TMG_SEED_SPAWN: row j is np.random.default_rng(np.random.SeedSequence(base,
+ *     spawn_key=key)) with key = (key0 + j,) for period == 0 — the j-th child
+ *     of SeedSequence(base).spawn(m) when key0 == 0 — and key = (key0 + j /
+ *     period, key1 + j % period) for period > 0: a (sample, global env) key
+ *     with period = the shard's env count and key1 = its first env, so shard
+ *     layouts agree.  seeds must be NULL.
+ * seed_words must be 1 or 2 either way.  OR one of TMG_SEED_STORE_* into mode
+ * to pick the kernel's store variant (diagnostic: the results are the same).
+ * m == 0 is a no-op; any context serves (a tmg_create_scan one too: only its
+ * device is used).  Refused: seed_words other than 1 or 2, a null rng,
+ * m < 0 or m > 2^31, period < 0, an unknown mode, a key element or (range
+ * form) a seed that would pass its width (2^64, 2^128) within the m rows.
+ * Asynchronous on `stream`. */
+#define TMG_SEED_INT   0
+#define TMG_SEED_SPAWN 1
+#define TMG_SEED_STORE_DIRECT 0x100   /* each lane stores its own row */
+#define TMG_SEED_STORE_STAGED 0x200   /* rows staged in LDS, coalesced stores */
+TMG_API int tmg_seed(tmg_ctx *ctx, int64_t m, int mode, const uint64_t *seeds, int seed_words,
+                     uint64_t base_lo, uint64_t base_hi, uint64_t key0, uint64_t key1, int64_t period,
+                     uint64_t *rng, void *stream);
+
 /* Replaces utils.compute_num_states (src/tile_match_gym/utils/utils.py:6-26) on
  * `device`: over all colours^(rows*cols) colourings of an all-normal board,
  * num_line_free = boards with no colour line, num_playable = those that also

@@ -3,7 +3,9 @@
 // uniform-over-effective-actions policy and the brute-force state count of
 // utils.compute_num_states.  Included by
 // tmg_capi.hip.  Both are plain HBM-streaming / integer kernels, one thread
-// per (env, cell) and one thread per run of boards respectively.
+// per (env, cell) and one thread per run of boards respectively.  And the
+// seeding of the envs' PCG64 streams (tmg_seed.h), one thread per stream.
+#include "tmg_seed.h"
 
 namespace tmg {
 
@@ -74,6 +76,41 @@ __global__ __launch_bounds__(BS) void sample_effective_kernel(int64_t n, int W, 
     }
     if (i >= n) return;
     actions[i] = draw_row(m, W, A, policy_draw(key, (uint64_t)(first_env + i), t));
+}
+
+// tmg_seed: the PCG64 words of np.random.default_rng(seed) /
+// default_rng(SeedSequence(base, spawn_key=...)) for m streams (seed_row,
+// tmg_seed.h), one lane per stream.  A row is five uint64 (40 B), so a lane
+// storing its own row writes 8 B at a 40 B stride, five times; with STAGE the
+// block's rows go through LDS ([BS][5] uint64, the block's contiguous 40 BS
+// bytes of rng) and leave as whole coalesced passes of 8 B per lane, the last
+// block's only up to row m.  Both are compiled in (TMG_SEED_STORE_*, tmg.h);
+// which one a plain call gets is TMG_SEED_LDS, picked by tools/seed_bench.py's
+// measurement.
+#ifndef TMG_SEED_BS
+#define TMG_SEED_BS 256
+#endif
+#ifndef TMG_SEED_LDS
+#define TMG_SEED_LDS 1
+#endif
+template <int BS, bool STAGE>
+__global__ __launch_bounds__(BS) void seed_kernel(SeedArgs a) {
+    __shared__ uint64_t rows[STAGE ? BS * 5 : 1];
+    const int64_t base = (int64_t)blockIdx.x * BS;
+    const int64_t j = base + threadIdx.x;
+    uint64_t w[5];
+    if (j < a.m) seed_row(a, j, w);
+    if constexpr (STAGE) {
+        if (j < a.m)
+            for (int q = 0; q < 5; q++) rows[threadIdx.x * 5 + q] = w[q];
+        __syncthreads();
+        const int cnt = (int)((a.m - base) < BS ? (a.m - base) : BS);
+        uint64_t *dst = a.rng + base * 5;
+        for (int q = threadIdx.x; q < cnt * 5; q += BS) dst[q] = rows[q];
+    } else {
+        if (j < a.m)
+            for (int q = 0; q < 5; q++) a.rng[j * 5 + q] = w[q];
+    }
 }
 
 // tmg_rollout's sums over the samples (launched behind the rollout kernels on

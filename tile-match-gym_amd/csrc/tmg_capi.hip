@@ -16,6 +16,7 @@
 #include "tmg_board.hip"
 #include "tmg_dispatch.h"
 #include "tmg_launch.h"
+#include "tmg_seed.h"
 
 #ifndef TMG_SRC_SHA
 #define TMG_SRC_SHA "unknown"
@@ -793,6 +794,23 @@ int tmg_sample_effective(tmg_ctx *ctx, int64_t n, const uint64_t *eff, uint64_t 
     return hip_check(hipGetLastError(), "kernel launch");
 }
 
+int tmg_seed(tmg_ctx *ctx, int64_t m, int mode, const uint64_t *seeds, int seed_words, uint64_t base_lo,
+             uint64_t base_hi, uint64_t key0, uint64_t key1, int64_t period, uint64_t *rng, void *stream) {
+    static_assert(TMG_SEED_SPAWN == tmg::kSeedSpawn && TMG_SEED_STORE_DIRECT == tmg::kSeedStoreDirect &&
+                      TMG_SEED_STORE_STAGED == tmg::kSeedStoreStaged && TMG_SEED_INT == 0,
+                  "tmg_seed.h's mode bits are tmg.h's");
+    if (!ctx) return fail(-1, "null context");
+    int rc = 0;
+    if (const char *why = tmg::seed_refusal(m, mode, seeds, seed_words, base_lo, base_hi, key0, key1, period, rng, &rc))
+        return fail(rc, why);
+    rc = set_device(ctx);
+    if (rc || m == 0) return rc;
+    const tmg::SeedArgs a{m, (mode & TMG_SEED_SPAWN) != 0, seeds, seed_words, base_lo, base_hi, key0, key1, period, rng};
+    tmg::launch_seed(reinterpret_cast<hipStream_t>(stream), a,
+                     mode & TMG_SEED_STORE_DIRECT ? 1 : mode & TMG_SEED_STORE_STAGED ? 2 : 0);
+    return hip_check(hipGetLastError(), "kernel launch");
+}
+
 int tmg_count_states(int device, int rows, int cols, int colours, uint64_t *num_playable, uint64_t *num_line_free) {
     if (!num_playable || !num_line_free) return fail(-1, "null output pointer");
     if (rows < 1 || cols < 1 || rows * cols > 16) return fail(-2, "count_states needs R*C <= 16");
@@ -843,7 +861,7 @@ __attribute__((visibility("default"))) int tmg_debug_cover(tmg_ctx *ctx, uint64_
 int tmg_num_actions(const tmg_ctx *ctx) { return ctx ? ctx->P.A : -1; }
 int tmg_mask_words(const tmg_ctx *ctx) { return ctx ? ctx->P.W : -1; }
 const char *tmg_last_error(void) { return g_err.c_str(); }
-int tmg_abi_version(void) { return 6; }
+int tmg_abi_version(void) { return 7; }
 const char *tmg_build_info(void) { return "src=" TMG_SRC_SHA ";variant=" TMG_VARIANT; }
 
 }  // extern "C"

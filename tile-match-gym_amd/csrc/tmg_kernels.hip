@@ -291,6 +291,13 @@ void launch_count_states(int R, int C, int k, uint64_t total, uint64_t per, uint
     hipLaunchKernelGGL(count_states_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, G, total, per,
                        counts);
 }
+void launch_seed(hipStream_t s, const SeedArgs &a, int store) {
+    constexpr int BS = TMG_SEED_BS;
+    const dim3 grid((unsigned)((a.m + BS - 1) / BS)), block(BS);
+    const bool stage = store ? store == 2 : TMG_SEED_LDS != 0;
+    if (stage) hipLaunchKernelGGL((seed_kernel<BS, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((seed_kernel<BS, false>), grid, block, 0, s, a);
+}
 void launch_rollout_reduce(hipStream_t s, int64_t n, int A, int samples, const int32_t *ret, int32_t *total,
                            int32_t *best_action, int32_t *best_total) {
     hipLaunchKernelGGL(rollout_reduce_kernel, env_grid(n), dim3(64), 0, s, n, A, samples, ret, total, best_action,

@@ -58,6 +58,9 @@ void launch_sample_effective(hipStream_t s, int64_t n, int W, int A, const uint6
                              int64_t first_env, int32_t t, int32_t *actions);
 void launch_count_states(int R, int C, int k, uint64_t total, uint64_t per, uint64_t threads,
                          unsigned long long *counts);
+// tmg_seed (tmg_seed.h); store: 0 the default variant, 1 direct, 2 staged
+struct SeedArgs;
+void launch_seed(hipStream_t s, const SeedArgs &a, int store);
 
 // tmg_peek (tmg_peek.hip): every action's outcome, no state written
 struct PeekArgs {

@@ -26,9 +26,10 @@ EXPORTS = ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_ste
            "tmg_onehot", "tmg_onehot_channels", "tmg_count_states", "tmg_sample_effective", "tmg_status",
            "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot", "tmg_plan_create", "tmg_plan_config",
            "tmg_plan_step", "tmg_plan_join", "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch",
-           "tmg_graph_destroy", "tmg_peek", "tmg_rollout")
+           "tmg_graph_destroy", "tmg_peek", "tmg_rollout", "tmg_seed")
 DTYPE_F32, DTYPE_U8, DTYPE_I32 = 0, 1, 2
-ABI_VERSION = 6
+ABI_VERSION = 7
+SEED_INT, SEED_SPAWN, SEED_STORE_DIRECT, SEED_STORE_STAGED = 0, 1, 0x100, 0x200
 STATUS_INTERNAL, STATUS_OVERFLOW, STATUS_CALLER = 1, 2, 4
 
 # CV_* branch counters of TMG_COVER builds (tmg_board.hip), in index order
@@ -44,10 +45,12 @@ SPECIAL_BITS = {"cookie": 1, "vertical_laser": 2, "horizontal_laser": 4, "bomb":
 FLAG_DONE, FLAG_COMBO, FLAG_SHUFFLED, FLAG_RESET, FLAG_OVERFLOW, FLAG_ERROR = 1, 2, 4, 8, 0x40, 0x80
 
 _libs = {}          # loaded libraries by path
+_M64 = (1 << 64) - 1
 
 P = ctypes.c_void_p
 I = ctypes.c_int
 I64 = ctypes.c_int64
+U64 = ctypes.c_uint64
 
 
 class TmgError(RuntimeError):
@@ -99,12 +102,13 @@ def load(path: str = None):
     L.tmg_graph_destroy.argtypes = [P]
     L.tmg_peek.argtypes = [P, I64, P, P, P, I, P, P, P, P, P, P, P]
     L.tmg_rollout.argtypes = [P, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32, P, P, P, P, P, P, P]
+    L.tmg_seed.argtypes = [P, I64, I, P, I, U64, U64, U64, U64, I64, P, P]
     for name in ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_step", "tmg_effective",
                  "tmg_num_actions", "tmg_mask_words", "tmg_abi_version", "tmg_onehot", "tmg_onehot_channels",
                  "tmg_sample_effective", "tmg_status", "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot",
                  "tmg_count_states", "tmg_plan_create", "tmg_plan_config", "tmg_plan_step", "tmg_plan_join",
                  "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy", "tmg_peek",
-                 "tmg_rollout"):
+                 "tmg_rollout", "tmg_seed"):
         getattr(L, name).restype = I
     if L.tmg_abi_version() != ABI_VERSION:
         raise TmgError("libtmg.so ABI version mismatch; rebuild it")
@@ -214,6 +218,21 @@ class Context:
         self._check(self._L.tmg_rollout(self._h, int(n), board, rng, timer, eff, int(trust_eff), int(depth),
                                         int(samples), int(key) % 2 ** 64, int(first_env), int(t), ret, plies, flags,
                                         total, best_action, best_total, stream))
+
+    def seed(self, m, rng, stream, mode=SEED_INT, seeds=None, seed_words=1, base=0, key0=0, key1=0, period=0):
+        """tmg_seed: the PCG64 words of m streams into rng ([m][5] uint64), seeded on the device as numpy
+        seeds them.  SEED_INT: default_rng(seed_j), seed_j from the device array `seeds` ([m] uint64, or
+        [m][2] lo / hi with seed_words=2) or, with seeds None, base + j.  SEED_SPAWN:
+        default_rng(SeedSequence(base, spawn_key=(key0 + j,))) or, with period > 0, spawn_key=(key0 + j //
+        period, key1 + j % period).  base: a non-negative int below 2^128."""
+        base = int(base)
+        if not 0 <= base < 1 << 128:
+            raise ValueError("base must be in [0, 2^128)")
+        key0, key1 = int(key0), int(key1)
+        if not (0 <= key0 < 1 << 64 and 0 <= key1 < 1 << 64):
+            raise ValueError("spawn key elements must be in [0, 2^64)")
+        self._check(self._L.tmg_seed(self._h, int(m), int(mode), seeds, int(seed_words), base & _M64, base >> 64,
+                                     key0, key1, int(period), rng, stream))
 
     def status(self, clear: bool = False) -> int:
         """Sticky STATUS_* bits of this context (waits for the device)."""

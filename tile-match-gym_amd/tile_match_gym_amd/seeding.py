@@ -41,6 +41,52 @@ def generator_from_words(words) -> np.random.Generator:
     return np.random.Generator(bg)
 
 
+def pack_seeds(seeds):
+    """How the device seeds `seeds` (tmg_seed, include/tmg.h), or None when only
+    the host can (batch_rng_words):
+
+        ("range", base, m)   consecutive ints base .. base + m - 1, nothing to upload
+        ("array", a)         a: uint64 (m,) for seeds below 2^64, else (m, 2) lo / hi
+
+    Taken: a range of step 1, and a list / tuple / integer ndarray (torch
+    tensors: pass their .cpu().numpy()) of non-negative ints below 2^128.  A
+    negative seed raises ValueError, as np.random.default_rng does.  Anything
+    else — a seed of 2^128 or more, a non-integer element, any other iterable,
+    which is left untouched — gives None."""
+    if isinstance(seeds, range):
+        if len(seeds) == 0:
+            return "range", 0, 0
+        if seeds.step != 1:
+            seeds = list(seeds)
+        elif seeds.start < 0:
+            raise ValueError("seeds must be non-negative")
+        elif seeds.stop > 1 << 128:
+            return None
+        else:
+            return "range", seeds.start, len(seeds)
+    if isinstance(seeds, np.ndarray) and seeds.dtype.kind in "iu":
+        if seeds.ndim != 1:
+            return None
+        if seeds.size and seeds.min() < 0:
+            raise ValueError("seeds must be non-negative")
+        return "array", np.ascontiguousarray(seeds.astype(np.uint64))
+    if isinstance(seeds, np.ndarray) and seeds.dtype == object and seeds.ndim == 1:
+        seeds = seeds.tolist()
+    if not isinstance(seeds, (list, tuple)):
+        return None
+    if not all(isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)) for s in seeds):
+        return None
+    vals = [int(s) for s in seeds]
+    if vals and min(vals) < 0:
+        raise ValueError("seeds must be non-negative")
+    top = max(vals, default=0)
+    if top < 1 << 64:
+        return "array", np.array(vals, dtype=np.uint64)
+    if top < 1 << 128:
+        return "array", np.array([[v & _M64, v >> 64] for v in vals], dtype=np.uint64)
+    return None
+
+
 def batch_rng_words(seeds) -> np.ndarray:
     """(N,5) uint64 state words for a sequence of integer seeds."""
     seeds = list(seeds)

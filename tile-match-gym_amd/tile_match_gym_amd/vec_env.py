@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .seeding import batch_rng_words, rng_words_from_seed
+from .seeding import batch_rng_words, pack_seeds, rng_words_from_seed
 
 CHECKPOINT_FORMAT = 1
 _STATE_ARRAYS = ("board", "rng", "timer", "eff")
@@ -93,7 +93,9 @@ class TileMatchVecEnv:
         self.board = torch.zeros((N, 2, num_rows, num_cols), dtype=torch.int8, **kw)
         if seeds is None:
             seeds = range(int(seed), int(seed) + N)
-        self.rng = torch.from_numpy(batch_rng_words(seeds).view(np.int64)).to(device)
+        self._dev_index = device.index if device.index is not None else torch.cuda.current_device()
+        self.rng = torch.empty((N, 5), dtype=torch.int64, **kw)
+        self._seed_rng(seeds)
         self.timer = torch.zeros(N, dtype=torch.int32, **kw)
         self.eff = torch.zeros((N, self.mask_words), dtype=torch.int64, **kw)
         self.reward = torch.zeros(N, dtype=torch.int32, **kw)
@@ -123,7 +125,6 @@ class TileMatchVecEnv:
         self._policy = (12345, 0)                   # (key, first_env) the policy plan is configured with
         self._vout = {}                             # extra outputs (set_step_outputs)
         self._held = []                             # action tensors the queued steps still read
-        self._dev_index = device.index if device.index is not None else torch.cuda.current_device()
         self._configure()
 
     # ----------------------------------------------------------------- API
@@ -179,10 +180,53 @@ class TileMatchVecEnv:
         self._configure()
 
     def set_seed(self, seeds):
-        """Re-seed every env (== tile_match_env.py:79-82 per env)."""
+        """Re-seed every env (== tile_match_env.py:79-82 per env): one seed per
+        env, as a range, a list / tuple, an integer ndarray or tensor (seeded on
+        the device, tmg_seed) or any other iterable of ints (seeded by numpy on
+        the host, as are seeds of 2^128 and more).  A negative seed raises
+        ValueError."""
         self.join()
-        w = batch_rng_words(seeds)
-        self.rng.copy_(torch.from_numpy(w.view(np.int64)))
+        self._seed_rng(seeds)
+
+    def _seed_rng(self, seeds):
+        """self.rng <- np.random.default_rng(seed) of every env's seed."""
+        N = self.num_envs
+        if isinstance(seeds, torch.Tensor):
+            seeds = seeds.detach().cpu().numpy()
+        how = pack_seeds(seeds)
+        if how is None:                            # only numpy can: the host loop
+            w = batch_rng_words(seeds)
+            if w.shape[0] != N:
+                raise ValueError(f"{w.shape[0]} seeds for {N} envs")
+            self.rng.copy_(torch.from_numpy(w.view(np.int64)))
+        elif how[0] == "range":
+            if how[2] != N:
+                raise ValueError(f"{how[2]} seeds for {N} envs")
+            self.ctx.seed(N, _ptr(self.rng), self._stream(), base=how[1])
+        else:
+            a = how[1]
+            if a.shape[0] != N:
+                raise ValueError(f"{a.shape[0]} seeds for {N} envs")
+            d = torch.from_numpy(a.view(np.int64)).to(self.device)
+            self.ctx.seed(N, _ptr(self.rng), self._stream(), seeds=_ptr(d), seed_words=a.ndim)
+
+    def fresh_rng(self, samples: int, entropy: int, first_env: int = 0) -> torch.Tensor:
+        """New PCG64 words for a sampled lookahead, seeded on the device
+        (tmg_seed): an (S, N, 5) int64 tensor whose row (s, i) is
+        np.random.default_rng(np.random.SeedSequence(entropy, spawn_key=(s,
+        first_env + i))), so a shard passing its global offset as first_env gets
+        the unsharded batch's streams.  entropy: a non-negative int below
+        2^128.  Enqueues on the current stream."""
+        samples, first_env = int(samples), int(first_env)
+        if samples < 1:
+            raise ValueError("samples must be >= 1")
+        if first_env < 0:
+            raise ValueError("first_env must be >= 0")
+        N = self.num_envs
+        w = torch.empty((samples, N, 5), dtype=torch.int64, device=self.device)
+        self.ctx.seed(samples * N, _ptr(w), self._stream(), mode=_native.SEED_SPAWN, base=entropy, key1=first_env,
+                      period=N)
+        return w
 
     def stagger_phases(self, blocks: int = 0, first_env: int = 0, interleave: bool = False, shift: int = 0):
         """Offset the episode phases right after a reset by setting timers.  A
@@ -315,7 +359,7 @@ class TileMatchVecEnv:
 
     _PEEK_OUTPUTS = {"reward": torch.int32, "n_new": torch.int32, "n_act": torch.int32, "flags": torch.uint8}
 
-    def peek(self, rng=None, outputs=("reward",), best: bool = False) -> dict:
+    def peek(self, rng=None, outputs=("reward",), best: bool = False, seed=None, first_env: int = 0) -> dict:
         """What a step with each action would report, for all A actions of every
         env at once, without changing any state (tmg_peek): Board.move on a copy
         of each board.  outputs: any of "reward", "n_new", "n_act" ((N, A)
@@ -325,13 +369,18 @@ class TileMatchVecEnv:
         rng=None simulates with the envs' own RNG streams, i.e. exactly what the
         next step will return; an (N, 5) int64 device tensor of other PCG64
         words gives a sampled lookahead that does not see the env's real
-        refills.  Joins, then enqueues on the current stream; the returned
-        tensors are reused by the next call."""
+        refills; seed=E (instead of rng) draws such words on the device,
+        fresh_rng(1, E, first_env)[0].  Joins, then enqueues on the current
+        stream; the returned tensors are reused by the next call."""
         self.join()
         for name in outputs:
             if name not in self._PEEK_OUTPUTS:
                 raise ValueError(f"unknown peek output {name!r}")
-        if rng is None:
+        if rng is not None and seed is not None:
+            raise ValueError("pass rng or seed, not both")
+        if seed is not None:
+            rng = self.fresh_rng(1, seed, first_env)[0]
+        elif rng is None:
             rng = self.rng
         elif rng.shape != (self.num_envs, 5) or rng.dtype != torch.int64 or rng.device != self.board.device \
                 or not rng.is_contiguous():
@@ -364,7 +413,7 @@ class TileMatchVecEnv:
     _ROLL_OUTPUTS = {"ret": torch.int32, "plies": torch.int32, "flags": torch.uint8, "total": torch.int32}
 
     def rollout(self, depth: int, samples: int = 1, rng=None, key: int = 12345, first_env: int = 0, t: int = 0,
-                horizon: bool = True, outputs=("ret",), best: bool = False) -> dict:
+                horizon: bool = True, outputs=("ret",), best: bool = False, seed=None) -> dict:
         """Policy rollouts of every action of every env, without changing any
         state (tmg_rollout): rollout (s, i, a) plays action a on a copy of
         board i with the RNG words rng[s, i], then continues with the examples'
@@ -379,7 +428,9 @@ class TileMatchVecEnv:
         total).  Ineffective actions and finished envs give zeros.  rng=None
         (samples == 1 only) simulates with the envs' own RNG streams, i.e. with
         the refills the env will really draw; otherwise a contiguous (S, N, 5)
-        int64 device tensor of PCG64 words ((N, 5) for S = 1).  Joins, then
+        int64 device tensor of PCG64 words ((N, 5) for S = 1), or seed=E for
+        fresh words drawn on the device, fresh_rng(samples, E, first_env): an
+        honest sampled lookahead with a new E per decision.  Joins, then
         enqueues on the current stream; the returned tensors are reused by the
         next call of the same samples."""
         self.join()
@@ -392,7 +443,11 @@ class TileMatchVecEnv:
             if name not in self._ROLL_OUTPUTS:
                 raise ValueError(f"unknown rollout output {name!r}")
         N, A = self.num_envs, self.num_actions
-        if rng is None:
+        if rng is not None and seed is not None:
+            raise ValueError("pass rng or seed, not both")
+        if seed is not None:
+            rng = self.fresh_rng(samples, seed, first_env)
+        elif rng is None:
             if samples != 1:
                 raise ValueError("rng=None (the envs' own streams) needs samples == 1: pass (S, N, 5) words")
             rng = self.rng
@@ -417,13 +472,13 @@ class TileMatchVecEnv:
         return {name: bufs[name] for name in names}
 
     def step_rollout_greedy(self, depth: int, samples: int = 1, rng=None, key: int = 12345, first_env: int = 0,
-                            t: int = 0, horizon: bool = True, fork: bool = True):
+                            t: int = 0, horizon: bool = True, fork: bool = True, seed=None):
         """Enqueue one step of the rollout-greedy policy: every env takes its
         lowest action of maximal summed rollout return (rollout(best=True) into
         self.actions; an env with no effective action takes action 0).
         Arguments as for rollout.  Returns that best total (N,) int32."""
         out = self.rollout(depth, samples, rng=rng, key=key, first_env=first_env, t=t, horizon=horizon, outputs=(),
-                           best=True)
+                           best=True, seed=seed)
         if self.actions is None:
             self.actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
         self.actions.copy_(out["best_action"])

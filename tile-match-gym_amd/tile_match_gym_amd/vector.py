@@ -109,7 +109,7 @@ class TileMatchVectorEnv:
         """Reset every env; `seed` (int) re-seeds env i with seed + i (list: one seed per env)."""
         v = self.vec
         if seed is not None:
-            seeds = list(seed) if isinstance(seed, (list, tuple, np.ndarray)) else range(int(seed), int(seed) + self.num_envs)
+            seeds = seed if isinstance(seed, (list, tuple, np.ndarray)) else range(int(seed), int(seed) + self.num_envs)
             v.set_seed(seeds)
         v.reset()
         if self._obs32 is not None:        # the step kernels keep it up to date from here on

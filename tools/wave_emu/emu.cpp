@@ -447,6 +447,18 @@ int emu_rollout(int R, int C, int k, int smask, int moves, int64_t n, const int8
     return 0;
 }
 
+// tmg_seed without the context and the stream: the same arguments and
+// refusals (-1 / -2), seed_row (tmg_seed.h) on every row in turn.  The store
+// variant bits of mode are accepted and change nothing here.
+int emu_seed(int64_t m, int mode, const uint64_t *seeds, int seed_words, uint64_t base_lo, uint64_t base_hi,
+             uint64_t key0, uint64_t key1, int64_t period, uint64_t *rng) {
+    int rc = 0;
+    if (tmg::seed_refusal(m, mode, seeds, seed_words, base_lo, base_hi, key0, key1, period, rng, &rc)) return rc;
+    const tmg::SeedArgs a{m, (mode & tmg::kSeedSpawn) != 0, seeds, seed_words, base_lo, base_hi, key0, key1, period, rng};
+    for (int64_t j = 0; j < m; j++) tmg::seed_row(a, j, rng + j * 5);
+    return 0;
+}
+
 unsigned long long emu_spills(void) { return g_spill_total; }
 int emu_cover_count(void) { return tmg::CV_COUNT; }
 void emu_cover(unsigned long long *out, int clear) {

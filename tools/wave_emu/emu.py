@@ -32,6 +32,8 @@ def load(asan=False):
     L.emu_peek_route.argtypes = [I, I, I, I, I, P]
     L.emu_rollout.argtypes = [I, I, I, I, I, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32,
                               P, P, P, P, P, P]
+    U64 = ctypes.c_uint64
+    L.emu_seed.argtypes = [I64, I, P, I, U64, U64, U64, U64, I64, P]
     return L
 
 
@@ -108,6 +110,25 @@ def rollout(L, R, C, k, smask, num_moves, board, rng, timer, eff, trust_eff, dep
                        *(out[f].ctypes.data for f in ("ret", "plies", "flags", "total", "best_action", "best_total")))
     if rc:
         raise ValueError(f"emu_rollout refused the call ({rc})")
+    return out
+
+
+SEED_INT, SEED_SPAWN = 0, 1
+
+
+def seed(L, m, mode=SEED_INT, seeds=None, seed_words=1, base=0, key0=0, key1=0, period=0):
+    """tmg_seed through the emulator's host loop over csrc/tmg_seed.h: the (m, 5)
+    uint64 PCG64 words.  seeds: None (the range / spawn forms) or a uint64
+    array of m * seed_words words; base: an int below 2^128.  A refused call
+    raises ValueError with the return code."""
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        assert seeds.size == m * seed_words
+    out = np.full((max(int(m), 0), 5), 0xA5A5A5A5A5A5A5A5, np.uint64)
+    rc = L.emu_seed(int(m), int(mode), seeds.ctypes.data if seeds is not None else None, int(seed_words),
+                    int(base) & (2 ** 64 - 1), int(base) >> 64, int(key0), int(key1), int(period), out.ctypes.data)
+    if rc:
+        raise ValueError(f"emu_seed refused the call ({rc})")
     return out
 
 

@@ -227,6 +227,13 @@ TMG_API int tmg_plan_create(tmg_plan **out, tmg_ctx *ctx, int64_t n, int8_t *boa
  *   board32 [n][2][R][C] int32: the boards in the reference's observation
  *     dtype (tile_match_env.py:52-77), kept up to date like action_mask
  *     (initialise it after a reset).
+ *   A finished env with autoreset 0 (timer == num_moves, nothing regenerates
+ *     it): the call that ends its episode writes terminated 1, moves_left 0
+ *     and an all-zero action_mask row; every later call is a step after done
+ *     (tile_match_env.py:94-95) and writes terminated {0, 0, 0, 1}, moves_left
+ *     0, reward / n_new / n_act 0, leaves the mask row all zero and the state
+ *     untouched, and raises TMG_STATUS_CALLER.  The policy draws such an
+ *     env's action over all A actions, its mask being empty.
  * Any output pointer may be NULL (not written). */
 TMG_API int tmg_plan_config(tmg_plan *plan, int autoreset, int policy, uint64_t key, int64_t first_env,
                             void *onehot, int onehot_dtype, uint8_t *terminated, uint8_t *action_mask,

@@ -4,6 +4,8 @@ tmg_sb.hip the boundaries).  Shared by tests/test_gpu_dispatch_cover.py (the
 device), tests/test_kernel_emulated.py and tests/test_overflow.py (the host
 wave emulator) and the census of tests/test_dispatch_route.py, which fails
 when a row that is the only cover of an instantiation is deleted.
+tests/fused_cases.py takes the whole list again for the fused step outputs
+(tests/test_gpu_fused.py, tests/test_fused_emulated.py and a census of their own).
 
 The row-plane cascade (rp_move) takes every lean move with R <= 16 and
 C <= 28; sb_move keeps the other no-specials boards of <= 128 cells with

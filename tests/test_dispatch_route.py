@@ -188,3 +188,36 @@ def test_every_instantiation_is_run(emu_lib):
     assert resets == ALL_RESETS - never, (f"never launched: {sorted(ALL_RESETS - never - resets)}, "
                                           f"not expected: {sorted(resets - (ALL_RESETS - never))}")
     assert len(sb_move) >= 4, sorted(sb_move)
+
+
+def test_every_instantiation_runs_with_fused_outputs(emu_lib):
+    """tests/fused_cases.py (test_gpu_fused.py on the device, test_fused_emulated.py
+    on the emulator) attaches every fused output of tmg_plan_config, in every
+    autoreset mode, and steps twice untrusted after a hand edit: together those
+    calls launch every step_kernel instantiation, and reach every reset_kernel
+    one as a deferred autoreset (but for dispatch_cases.NEVER_RUN_RESETS), with
+    the outputs attached.  None goes to the lane kernel, which writes no fused
+    output: the policy steps stay on the wave kernels."""
+    import dispatch_cases as dc
+    import fused_cases as fc
+    emu, L = emu_lib
+    assert fc.MODE_CODE == {"none": 0, "same_step": 1, "next_step": 2}
+    steps, deferred = set(), set()
+    for shape in fc.SHAPES:
+        for mode in fc.MODES:
+            calls = [dict(), dict(policy=True), dict(trust_eff=0)]      # the plain, the policy and the hand-edit steps
+            for call in calls:
+                for n in (67, 203, LANE_MIN):                            # the tests' batches; and were they large
+                    st, rt = emu.route(L, *shape, mode=fc.MODE_CODE[mode], n=n, have_lane=True, fused=FUSED, **call)
+                    assert not st["lane"], (shape, mode, call, n)
+                    if n == LANE_MIN:
+                        continue
+                    steps.add(tuple(st[f] for f in ("MAXN", "GEN", "NB", "CODD", "FIX")))
+                    if st["deferred"]:
+                        assert mode != "none"
+                        deferred.add(tuple(rt[f] for f in ("MAXN", "NB", "CODD", "FIX")))
+    never = {(m, nb, codd, NOFIX) for m, nb, codd, _ in dc.NEVER_RUN_RESETS}
+    assert len(ALL_STEPS) == 23
+    assert steps == ALL_STEPS, f"never launched: {sorted(ALL_STEPS - steps)}, not in the ladders: {sorted(steps - ALL_STEPS)}"
+    assert deferred == ALL_RESETS - never, (f"never deferred: {sorted(ALL_RESETS - never - deferred)}, "
+                                            f"not expected: {sorted(deferred - (ALL_RESETS - never))}")

@@ -23,10 +23,13 @@ def mask_bytes(eff, A):
 
 
 class VectorOracle:
-    """mode "next_step" (an env that ended last step is reset instead of stepped)
-    or "same_step" (an ending env is reset in the same step; final boards kept)."""
+    """mode "next_step" (an env that ended last step is reset instead of stepped),
+    "same_step" (an ending env is reset in the same step; final boards kept) or
+    "none" (nothing is regenerated: a finished env reports the step-after-done
+    error in terminated[:, 3], with an all-zero mask row and 0 moves left)."""
 
     def __init__(self, o, mode):
+        assert mode in ("none", "same_step", "next_step"), mode
         self.o, self.mode = o, mode
         self.A = 2 * o.R * o.C - o.R - o.C
         self.pending = np.zeros(o.board.shape[0], bool)
@@ -44,7 +47,7 @@ class VectorOracle:
         if self.mode == "next_step":
             reset_subset(o, np.nonzero(self.pending)[0])
             self.pending = term.copy()
-        else:
+        elif self.mode == "same_step":
             out["final_board"] = o.board.copy()
             reset_subset(o, np.nonzero(term)[0])
         out["action_mask"] = mask_bytes(o.eff, self.A)

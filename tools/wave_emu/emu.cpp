@@ -465,6 +465,12 @@ void emu_cover(unsigned long long *out, int clear) {
     for (int i = 0; i < tmg::CV_COUNT; i++) { out[i] = g_cover[i]; if (clear) g_cover[i] = 0; }
 }
 unsigned emu_status(void) { return (g_status[0] ? 1u : 0u) | (g_status[1] ? 2u : 0u) | (g_status[2] ? 4u : 0u); }
+// tmg_status with clear != 0: the sticky bits so far, then none
+unsigned emu_status_clear(void) {
+    const unsigned st = emu_status();
+    for (uint32_t &s : g_status) s = 0;
+    return st;
+}
 
 int emu_reset(int R, int C, int k, int smask, int moves, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer,
               uint64_t *eff) {

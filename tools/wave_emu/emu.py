@@ -25,6 +25,7 @@ def load(asan=False):
     L.emu_effective.argtypes = [I, I, I, I, I64, P, P]
     L.emu_spills.restype = ctypes.c_ulonglong
     L.emu_status.restype = ctypes.c_uint
+    L.emu_status_clear.restype = ctypes.c_uint
     L.emu_cover.argtypes = [P, I]
     L.emu_cover.restype = None
     L.emu_route.argtypes = [I, I, I, I, I, I, I64, I, I, I, P, P]

@@ -17,10 +17,28 @@ SHAPES = list(dispatch_cases.CASES) + [dispatch_cases.ROW_PLANE_CONTROL] + EXTRA
 # the adversarial boards of the untrusted / spill tests (tests/adversarial.py)
 ADVERSARIAL_SHAPES = [(20, 20, 6, 15), (10, 10, 4, 14), (8, 8, 3, 15)]
 
+# laser_sea boards, every one of which spills, more of them than a spill launch
+# has waves (kSpillWaves, csrc/tmg_board.hip): a wave of the drain then takes a
+# second env and reuses its workspace.  shape -> envs for peek, for rollout (at
+# 2 samples, depth 2); the 512-cell family on the device only (the emulator
+# needs about a minute for it)
+SPILL_WAVES = 16          # kSpillWaves: raise both together, and the env counts below past it
+MANY_SPILLS = {(10, 10, 4, 14): (24, 12), (20, 20, 6, 15): (20, 10)}
+
 FLAG_COMBO, FLAG_SHUFFLED, FLAG_ERROR = 2, 4, 0x80
 FIELDS = ("reward", "n_new", "n_act", "flags", "best_action", "best_reward")
 
 case_id = dispatch_cases.case_id
+
+
+def spill_params(device):
+    """(shape, mode, many) of the untrusted / spill tests: every mode on every
+    adversarial shape with envs_of(shape) envs, then MANY_SPILLS."""
+    import pytest
+    from adversarial import MODES
+    ps = [pytest.param(s, m, False, id=f"{case_id(s)}-{m}") for m in MODES for s in ADVERSARIAL_SHAPES]
+    return ps + [pytest.param(s, "laser_sea", True, id=f"{case_id(s)}-laser_sea-many") for s in MANY_SPILLS
+                 if device or s[0] * s[1] <= 128]
 
 
 def envs_of(shape):

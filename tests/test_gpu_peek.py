@@ -10,7 +10,7 @@ import torch
 
 import dispatch_cases as dc
 import peek_cases
-from adversarial import MODES, adversarial_boards
+from adversarial import adversarial_boards
 from deep_rollouts import COVER_LIB, specials
 from oracle import oracle as orc
 from peek_cases import assert_peek_equal, oracle_peek
@@ -123,15 +123,14 @@ def test_peek_agrees_with_next_step(shape):
     env.close()
 
 
-@pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("shape", peek_cases.ADVERSARIAL_SHAPES, ids=peek_cases.case_id)
-def test_peek_untrusted_and_spill_gpu(mode, shape):
+@pytest.mark.parametrize("shape,mode,many", peek_cases.spill_params(device=True))
+def test_peek_untrusted_and_spill_gpu(shape, mode, many):
     """Hand-written boards, trust_eff = 0 and no mask given: the general
     kernels, and the spill pass for the envs one of whose actions outgrows the
-    LDS lists."""
+    LDS lists.  many: more spilling envs than the spill pass has waves."""
     from tile_match_gym_amd.seeding import batch_rng_words
     R, C, k, sm = shape
-    n = peek_cases.envs_of(shape)
+    n = peek_cases.MANY_SPILLS[shape][0] if many else peek_cases.envs_of(shape)
     b = adversarial_boards(n, R, C, k, sm, 11, mode)
     words = batch_rng_words(range(300, 300 + n))
     env = _env(shape, n)
@@ -148,6 +147,8 @@ def test_peek_untrusted_and_spill_gpu(mode, shape):
     assert env.status() == 0
     if (R, C) in ((20, 20), (10, 10)) and mode != "stripes":
         assert env.ctx.spills() > s0, "the adversarial boards were meant to outgrow the LDS lists"
+    if many:
+        assert env.ctx.spills() - s0 > peek_cases.SPILL_WAVES
     if mode == "combo_grid":
         assert (got["flags"] & peek_cases.FLAG_COMBO).any()
     assert np.array_equal(board.cpu().numpy(), b) and np.array_equal(rng.cpu().numpy().view(np.uint64), words)

@@ -12,7 +12,7 @@ import torch
 import dispatch_cases as dc
 import peek_cases
 import rollout_cases as rc
-from adversarial import MODES, adversarial_boards
+from adversarial import adversarial_boards
 from deep_rollouts import COVER_LIB, specials
 from oracle import oracle as orc
 from peek_cases import oracle_peek
@@ -188,16 +188,16 @@ def test_rollout_agrees_with_real_steps(shape):
     one.close()
 
 
-@pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("shape", peek_cases.ADVERSARIAL_SHAPES, ids=peek_cases.case_id)
-def test_rollout_untrusted_and_spill_gpu(mode, shape):
+@pytest.mark.parametrize("shape,mode,many", peek_cases.spill_params(device=True))
+def test_rollout_untrusted_and_spill_gpu(shape, mode, many):
     """Hand-written boards, trust_eff = 0 and no mask given, through
     Context.rollout: the general kernels, and the spill pass for the virtual
-    envs one of whose plies outgrows the LDS lists."""
+    envs one of whose plies outgrows the LDS lists.  many: more spilling
+    virtual envs than the spill pass has waves."""
     from tile_match_gym_amd.seeding import batch_rng_words
     R, C, k, sm = shape
-    n = peek_cases.envs_of(shape)
-    depth, samples = 3, 2
+    n = peek_cases.MANY_SPILLS[shape][1] if many else peek_cases.envs_of(shape)
+    depth, samples = 2 if many else 3, 2
     b = adversarial_boards(n, R, C, k, sm, 11, mode)
     words = np.stack([batch_rng_words(range(300, 300 + n)), batch_rng_words(range(340, 340 + n))])
     env = _env(shape, n)
@@ -217,6 +217,8 @@ def test_rollout_untrusted_and_spill_gpu(mode, shape):
     assert env.status() == 0
     if (R, C) in ((20, 20), (10, 10)) and mode != "stripes":
         assert env.ctx.spills() > s0, "the adversarial boards were meant to outgrow the LDS lists"
+    if many:
+        assert env.ctx.spills() - s0 > peek_cases.SPILL_WAVES
     if mode == "combo_grid":
         assert (got["flags"] & rc.FLAG_COMBO).any()
     assert np.array_equal(board.cpu().numpy(), b) and np.array_equal(rng.cpu().numpy().view(np.uint64), words)

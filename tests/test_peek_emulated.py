@@ -12,7 +12,7 @@ import pytest
 
 import dispatch_cases
 import peek_cases
-from adversarial import MODES, adversarial_boards
+from adversarial import adversarial_boards
 from peek_cases import assert_peek_equal, oracle_peek
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,16 +46,16 @@ def test_peek_vs_oracle(emu_lib, shape):
     assert L.emu_status() == 0
 
 
-@pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("shape", peek_cases.ADVERSARIAL_SHAPES, ids=peek_cases.case_id)
-def test_peek_untrusted_and_spill(emu_lib, mode, shape):
+@pytest.mark.parametrize("shape,mode,many", peek_cases.spill_params(device=False))
+def test_peek_untrusted_and_spill(emu_lib, shape, mode, many):
     """Hand-written boards (they may hold lines and any special), no mask
     given: the kernel scans its own, the general kernels run, and an env one
-    of whose actions outgrows the LDS lists is re-run whole by the spill pass."""
+    of whose actions outgrows the LDS lists is re-run whole by the spill pass.
+    many: more spilling envs than the spill pass has waves."""
     from tile_match_gym_amd.seeding import batch_rng_words
     emu, L = emu_lib
     R, C, k, sm = shape
-    n = peek_cases.envs_of(shape)
+    n = peek_cases.MANY_SPILLS[shape][0] if many else peek_cases.envs_of(shape)
     b = adversarial_boards(n, R, C, k, sm, 11, mode)
     words = batch_rng_words(range(300, 300 + n))
     s0 = L.emu_spills()
@@ -64,6 +64,8 @@ def test_peek_untrusted_and_spill(emu_lib, mode, shape):
     assert L.emu_status() == 0
     if (R, C) in ((20, 20), (10, 10)) and mode != "stripes":
         assert L.emu_spills() > s0, "the adversarial boards were meant to outgrow the LDS lists"
+    if many:
+        assert L.emu_spills() - s0 > peek_cases.SPILL_WAVES
     if mode == "combo_grid":
         assert (got["flags"] & peek_cases.FLAG_COMBO).any()
 

@@ -14,7 +14,7 @@ import pytest
 import dispatch_cases
 import peek_cases
 import rollout_cases as rc
-from adversarial import MODES, adversarial_boards
+from adversarial import adversarial_boards
 from peek_cases import oracle_peek
 from rollout_cases import assert_rollout_equal, oracle_rollout
 
@@ -111,18 +111,18 @@ def orc_mask(board):
     return orc.effective_mask(board)[0]
 
 
-@pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("shape", peek_cases.ADVERSARIAL_SHAPES, ids=peek_cases.case_id)
-def test_rollout_untrusted_and_spill(emu_lib, mode, shape):
+@pytest.mark.parametrize("shape,mode,many", peek_cases.spill_params(device=False))
+def test_rollout_untrusted_and_spill(emu_lib, shape, mode, many):
     """Hand-written boards (they may hold lines and any special), no mask
     given: ply 0 scans its own mask and searches the whole board for lines, the
     general kernels run, and a virtual env one of whose plies outgrows the LDS
-    lists is re-run whole by the spill pass."""
+    lists is re-run whole by the spill pass.  many: more spilling virtual envs
+    than the spill pass has waves."""
     from tile_match_gym_amd.seeding import batch_rng_words
     emu, L = emu_lib
     R, C, k, sm = shape
-    n = peek_cases.envs_of(shape)
-    depth, samples = 3, 2
+    n = peek_cases.MANY_SPILLS[shape][1] if many else peek_cases.envs_of(shape)
+    depth, samples = 2 if many else 3, 2
     b = adversarial_boards(n, R, C, k, sm, 11, mode)
     words = np.stack([batch_rng_words(range(300, 300 + n)), batch_rng_words(range(340, 340 + n))])
     s0 = L.emu_spills()
@@ -136,6 +136,8 @@ def test_rollout_untrusted_and_spill(emu_lib, mode, shape):
     if (R, C) in ((20, 20), (10, 10)) and mode != "stripes":
         assert L.emu_spills() > s0, "the adversarial boards were meant to outgrow the LDS lists"
         assert c["roll_spill"] > 0, c
+    if many:
+        assert L.emu_spills() - s0 > peek_cases.SPILL_WAVES
     if mode == "combo_grid":
         assert (got["flags"] & rc.FLAG_COMBO).any()
 

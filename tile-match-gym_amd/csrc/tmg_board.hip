@@ -96,6 +96,7 @@ constexpr int kMaxShuffles = 1 << 12;   // shuffles per loop
 // Per-stream queue of the envs whose step ran out of LDS list space
 // (step_env), drained by spill_kernel.  Sized by the host for the envs of
 // the launch (cap >= n), so every such env fits: no step is ever dropped.
+// tests/peek_cases.py repeats the value (SPILL_WAVES): its cases queue more envs than this
 constexpr int kSpillWaves = 16;          // spill_kernel workgroups (one wave, one WsSerialBig each)
 struct SpillQ {
     uint32_t count, done;        // queued envs; spill_kernel waves finished
@@ -2599,17 +2600,26 @@ __device__ __forceinline__ int board_move(const Params &P, WS &w, int lane, cons
 }
 
 // ------------------------------------------------------------------ kernels
-__device__ __forceinline__ LaneJump load_jump(const Params &P, int lane, const Rng &g) {
-    const uint64_t *t = P.jump + lane * 4;
+// A lane's jump-table row in two halves: step_env issues the loads early and
+// finishes late.  rowp: the row-plane cascade (tmg_rp.hip) draws in
+// bp_ring_fill's lane order, so lane l takes the row of output bp_out(l).
+struct JumpRow { uint64_t a0, a1, g0, g1; };
+__device__ __forceinline__ JumpRow jump_row_load(const Params &P, int l, bool rowp) {
+    const uint64_t *t = P.jump + (rowp ? bp_out(l) : l) * 4;
+    return JumpRow{t[0], t[1], t[2], t[3]};
+}
+__device__ __forceinline__ LaneJump jump_row_finish(const JumpRow &r, const Rng &g) {
     LaneJump J;
-    J.Aj = U128{t[0], t[1]};
-    J.Gj = U128{t[2], t[3]};
+    J.Aj = U128{r.a0, r.a1};
+    J.Gj = U128{r.g0, r.g1};
     J.incG = mul128(U128{g.ilo, g.ihi}, J.Gj);
     return J;
 }
-// the same in bp_ring_fill's lane order: the row of output bp_out(lane) (tmg_rp.hip)
-__device__ __forceinline__ LaneJump load_jump_bp(const Params &P, int lane, const Rng &g) {
-    return load_jump(P, bp_out(lane), g);
+__device__ __forceinline__ LaneJump load_jump(const Params &P, int lane, const Rng &g, bool rowp = false) {
+    return jump_row_finish(jump_row_load(P, lane, rowp), g);
+}
+__device__ __forceinline__ LaneJump load_jump_bp(const Params &P, int lane, const Rng &g) {   // tmg_rp.hip's
+    return load_jump(P, lane, g, true);
 }
 
 __device__ __forceinline__ Rng load_rng(const uint64_t *p) {
@@ -2762,14 +2772,10 @@ __device__ __forceinline__ uint32_t step_env(
     const uint32_t bw = bwhole ? reinterpret_cast<const uint32_t *>(gb)[lane < nbw ? lane : 0] : 0u;
     const uint64_t *rp = rng + e * 5;
     const uint64_t q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3], q4 = rp[4];
-    // the row-plane cascade (tmg_rp.hip) draws in bp_ring_fill's lane order:
-    // J is then the table row of output bp_out(lane), and the rare users of
-    // the linear order below reload theirs (load_jump)
-    constexpr bool RP = SBNB > 0 && !GEN;
+    // with rowp the rare users of the linear order below reload theirs (load_jump)
     bool rowp = false;
-    if constexpr (RP) rowp = rp_shape(P);
-    const uint64_t *jt = P.jump + (rowp ? bp_out(lane) : lane) * 4;
-    const uint64_t j0 = jt[0], j1 = jt[1], j2 = jt[2], j3 = jt[3];
+    if constexpr (SBNB > 0 && !GEN) rowp = rp_shape(P);
+    const JumpRow jrow = jump_row_load(P, lane, rowp);
     if (bwhole) {
         if (lane < nbw) reinterpret_cast<uint32_t *>(w.brd)[lane] = bw;
     } else {
@@ -2797,15 +2803,12 @@ __device__ __forceinline__ uint32_t step_env(
     }
     Rng g;
     g.slo = bcast64(q0); g.shi = bcast64(q1); g.ilo = bcast64(q2); g.ihi = bcast64(q3); g.h = bcast64(q4);
-    LaneJump J;
-    J.Aj = U128{j0, j1};
-    J.Gj = U128{j2, j3};
-    J.incG = mul128(U128{g.ilo, g.ihi}, J.Gj);
+    LaneJump J = jump_row_finish(jrow, g);
     const Cells<MAXN / 64> cl = make_cells<MAXN / 64>(P, lane);
     int elim = 0, nn = 0, na = 0;
     bool changed = false;
     if (effective) {
-        if constexpr (RP) {
+        if constexpr (SBNB > 0 && !GEN) {
             if (rowp) elim = rp_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags);
             else elim = sb_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags, e);
         } else elim = board_move<MAXN, GEN, SBNB, CODD, TIER>(P, w, lane, J, g, cl, p1, p2, flags, nn, na, e, lists,
@@ -2965,23 +2968,20 @@ __global__ __launch_bounds__(64, MAXN == 128 ? (GEN ? kGen128Waves : (FIX != kNo
     note_status(P, lane, st);
 }
 
-// Re-runs the steps the general step kernel queued on running out of LDS list
-// space (step_env, FL_OVF), on global-memory lists sized for the worst case
-// (WsSerialBig): launched right after every general step launch on the same
-// stream with the same buffers, kSpillWaves one-wave workgroups, each
-// with its own WsSerialBig.  An empty queue costs one load per wave.  The
-// generic (non-bitboard) path: bit-identical results by construction.
+// The spill tier of step / peek / rollout: re-runs what a general launch queued
+// on running out of LDS list space (FL_OVF) on global-memory lists sized for
+// the worst case (WsSerialBig).  Launched right after every general launch on
+// the same stream with the same buffers: kSpillWaves one-wave workgroups, each
+// with its own WsSerialBig, striding over the queued ids below `limit`.
+// body(w, lane, id, lists) re-runs one id whole on the generic (non-bitboard)
+// path, bit-identical by construction, and returns its ST_* bits.  An empty
+// queue costs one load per wave.
 // Small footprint on purpose (no LDS lists, at most 8 waves/SIMD's worth of
-// VGPRs, spilling to scratch instead): the launch follows every
-// general step on its stream and must find room on a chip busy with the
-// other streams' kernels at once, or it holds its stream back; the rare
-// steps it re-runs may go slowly.
-template <int MAXN>
-__global__ __launch_bounds__(64, 8) void spill_kernel(
-    Params P, int64_t n, int8_t *__restrict__ board, uint64_t *__restrict__ rng, int32_t *__restrict__ timer,
-    const int32_t *__restrict__ actions, int32_t *__restrict__ reward, int32_t *__restrict__ n_new,
-    int32_t *__restrict__ n_act, uint8_t *__restrict__ flags_out, uint64_t *__restrict__ eff, int trust_eff,
-    int autoreset) {
+// VGPRs, spilling to scratch instead): the launch must find room on a chip
+// busy with the other streams' kernels at once, or it holds its stream back;
+// the rare work it re-runs may go slowly.
+template <int MAXN, class Body>
+__device__ __forceinline__ void spill_drain(const Params &P, int64_t limit, Body body) {
     TMG_SMEM_DECL(smem);
     using WS = Ws<MAXN, false>;                   // the lists are global (WsSerialBig)
     const int lane = threadIdx.x & 63;
@@ -2992,12 +2992,10 @@ __global__ __launch_bounds__(64, 8) void spill_kernel(
     const int cnt = (int)(queued < q->cap ? queued : q->cap);
     int done = 0;
     for (int i = (int)blockIdx.x; i < cnt; i += (int)gridDim.x) {
-        const int64_t e = (int64_t)bcast64((uint64_t)q->env[i]);
-        if (e < 0 || e >= n) continue;
-        WSYNC();
-        const uint32_t st = step_env<MAXN, true, 0, false, TIER_SPILL, WS, WsSerialBig<MAXN>>(
-            P, w, lane, e, board, rng, timer, actions, reward, n_new, n_act, flags_out, eff, trust_eff, autoreset, lists);
-        note_status(P, lane, st);
+        const int64_t id = (int64_t)bcast64((uint64_t)q->env[i]);
+        if (id < 0 || id >= limit) continue;
+        WSYNC();                                   // the id before is done with the workspace
+        note_status(P, lane, body(w, lane, id, lists));
         done++;
     }
     if (lane == 0) {
@@ -3005,6 +3003,19 @@ __global__ __launch_bounds__(64, 8) void spill_kernel(
         __threadfence();
         if (atomicAdd(&q->done, 1u) == gridDim.x - 1) { q->count = 0u; q->done = 0u; }   // the last wave empties the queue
     }
+}
+
+// the steps step_kernel<*, true> queued
+template <int MAXN>
+__global__ __launch_bounds__(64, 8) void spill_kernel(
+    Params P, int64_t n, int8_t *__restrict__ board, uint64_t *__restrict__ rng, int32_t *__restrict__ timer,
+    const int32_t *__restrict__ actions, int32_t *__restrict__ reward, int32_t *__restrict__ n_new,
+    int32_t *__restrict__ n_act, uint8_t *__restrict__ flags_out, uint64_t *__restrict__ eff, int trust_eff,
+    int autoreset) {
+    spill_drain<MAXN>(P, n, [&](Ws<MAXN, false> &w, int lane, int64_t e, WsSerialBig<MAXN> *lists) {
+        return step_env<MAXN, true, 0, false, TIER_SPILL, Ws<MAXN, false>, WsSerialBig<MAXN>>(
+            P, w, lane, e, board, rng, timer, actions, reward, n_new, n_act, flags_out, eff, trust_eff, autoreset, lists);
+    });
 }
 
 // TileMatchEnv.reset without a seed (tile_match_env.py:84-91) of env e

@@ -38,12 +38,9 @@ __device__ __forceinline__ void peek_load(const Params &P, const uint64_t *__res
                                           int ll, Rng &g, LaneJump &J) {
     const uint64_t *rp = rng + e * 5 + (ll >> 6);          // ll < 64: the lane index only keeps the loads per action
     const uint64_t q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3], q4 = rp[4];
-    const uint64_t *jt = P.jump + (rowp ? bp_out(ll) : ll) * 4;
-    const uint64_t j0 = jt[0], j1 = jt[1], j2 = jt[2], j3 = jt[3];
+    const JumpRow jrow = jump_row_load(P, ll, rowp);       // all nine loads before the first broadcast waits
     g.slo = bcast64(q0); g.shi = bcast64(q1); g.ilo = bcast64(q2); g.ihi = bcast64(q3); g.h = bcast64(q4);
-    J.Aj = U128{j0, j1};
-    J.Gj = U128{j2, j3};
-    J.incG = mul128(U128{g.ilo, g.ihi}, J.Gj);
+    J = jump_row_finish(jrow, g);
 }
 
 // Board.move (board.py:330-395) of every action of env e, each on a copy.
@@ -193,39 +190,15 @@ __global__ __launch_bounds__(64, MAXN == 128 ? (GEN ? kPeekGen128Waves : kPeekLe
     note_status(P, lane, st);
 }
 
-// Re-runs every action of the envs a general peek launch queued (an action's
-// cascade outgrew the LDS lists) on the worst-case global-memory lists, and
-// writes all of those envs' outputs: spill_kernel's shape (kSpillWaves
-// one-wave workgroups, each with its WsSerialBig of P.spill_ws; the generic
-// non-bitboard path; the last wave empties the queue), launched after every
-// general peek launch on its stream.
+// every action of the envs peek_kernel<*, true> queued, and all of those envs' outputs (spill_drain)
 template <int MAXN>
 __global__ __launch_bounds__(64, 8) void peek_spill_kernel(
     Params P, int64_t n, const int8_t *__restrict__ board, const uint64_t *__restrict__ rng,
     const uint64_t *__restrict__ eff, int trust_eff, int32_t *__restrict__ reward, int32_t *__restrict__ n_new,
     int32_t *__restrict__ n_act, uint8_t *__restrict__ flags_out, int32_t *__restrict__ best_action,
     int32_t *__restrict__ best_reward) {
-    TMG_SMEM_DECL(smem);
-    using WS = Ws<MAXN, false>;                   // the lists are global (WsSerialBig)
-    const int lane = threadIdx.x & 63;
-    WS &w = *reinterpret_cast<WS *>(smem);
-    SpillQ *q = P.spill;
-    WsSerialBig<MAXN> *lists = reinterpret_cast<WsSerialBig<MAXN> *>(P.spill_ws) + blockIdx.x;
-    const int64_t queued = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)q->count);
-    const int cnt = (int)(queued < q->cap ? queued : q->cap);
-    int done = 0;
-    for (int i = (int)blockIdx.x; i < cnt; i += (int)gridDim.x) {
-        const int64_t e = (int64_t)bcast64((uint64_t)q->env[i]);
-        if (e < 0 || e >= n) continue;
-        WSYNC();
-        const uint32_t st = peek_env<MAXN, true, 0, false, TIER_SPILL, WS, WsSerialBig<MAXN>>(
+    spill_drain<MAXN>(P, n, [&](Ws<MAXN, false> &w, int lane, int64_t e, WsSerialBig<MAXN> *lists) {
+        return peek_env<MAXN, true, 0, false, TIER_SPILL, Ws<MAXN, false>, WsSerialBig<MAXN>>(
             P, w, lane, e, board, rng, eff, trust_eff, reward, n_new, n_act, flags_out, best_action, best_reward, lists);
-        note_status(P, lane, st);
-        done++;
-    }
-    if (lane == 0) {
-        if (done) atomicAdd(&q->total, (unsigned long long)done);
-        __threadfence();
-        if (atomicAdd(&q->done, 1u) == gridDim.x - 1) { q->count = 0u; q->done = 0u; }   // the last wave empties the queue
-    }
+    });
 }

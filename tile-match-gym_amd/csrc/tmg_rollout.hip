@@ -59,16 +59,6 @@ __device__ __forceinline__ void roll_store_word(const Params &P, const RollArgs 
     }
 }
 
-// lane ll's jump-table row for a stream of increment g.inc (peek_load's, the
-// RNG words apart: those run on from ply to ply)
-__device__ __forceinline__ void roll_jump(const Params &P, bool rowp, int ll, const Rng &g, LaneJump &J) {
-    const uint64_t *jt = P.jump + (rowp ? bp_out(ll) : ll) * 4;
-    const uint64_t j0 = jt[0], j1 = jt[1], j2 = jt[2], j3 = jt[3];
-    J.Aj = U128{j0, j1};
-    J.Gj = U128{j2, j3};
-    J.incG = mul128(U128{g.ilo, g.ihi}, J.Gj);
-}
-
 // Every action's rollout of virtual env v.  Template parameters as peek_env;
 // returns the ST_* bits for the sticky status word.  TIER_MAIN with GEN: the
 // first ply whose cascade outgrows the LDS lists queues v for
@@ -129,7 +119,7 @@ __device__ __forceinline__ uint32_t rollout_env(const Params &P, const RollArgs 
     const uint64_t *rv = a.rng + v * 5;
     if constexpr (!RELOAD) {
         g0 = load_rng(rv);
-        roll_jump(P, rowp, lane, g0, J0);
+        J0 = load_jump(P, lane, g0, rowp);
         cl0 = make_cells<MAXN / 64>(P, lane);
     }
     const uint64_t gid = (uint64_t)(P.pol_first + e);
@@ -165,7 +155,7 @@ __device__ __forceinline__ uint32_t rollout_env(const Params &P, const RollArgs 
                 Cells<MAXN / 64> cl = cl0;
                 if constexpr (RELOAD) {
                     const int ll = loop_lane(lane);
-                    roll_jump(P, rowp, ll, g, J);
+                    J = load_jump(P, ll, g, rowp);
                     cl = make_cells<MAXN / 64>(P, ll);
                 }
                 if constexpr (GEN) {
@@ -239,33 +229,10 @@ __global__ __launch_bounds__(64, MAXN == 128 ? (GEN ? kRollGen128Waves : kRollLe
     note_status(P, lane, st);
 }
 
-// Re-runs every rollout of the virtual envs a general launch queued (a ply's
-// cascade outgrew the LDS lists) on the worst-case global-memory lists:
-// peek_spill_kernel's shape, launched after every general rollout launch on
-// its stream.
+// every rollout of the virtual envs rollout_kernel<*, true> queued (spill_drain)
 template <int MAXN>
 __global__ __launch_bounds__(64, 8) void rollout_spill_kernel(Params P, RollArgs a) {
-    TMG_SMEM_DECL(smem);
-    using WS = Ws<MAXN, false>;                   // the lists are global (WsSerialBig)
-    const int lane = threadIdx.x & 63;
-    WS &w = *reinterpret_cast<WS *>(smem);
-    SpillQ *q = P.spill;
-    WsSerialBig<MAXN> *lists = reinterpret_cast<WsSerialBig<MAXN> *>(P.spill_ws) + blockIdx.x;
-    const int64_t queued = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)q->count);
-    const int cnt = (int)(queued < q->cap ? queued : q->cap);
-    const int64_t nv = a.n * a.samples;
-    int done = 0;
-    for (int i = (int)blockIdx.x; i < cnt; i += (int)gridDim.x) {
-        const int64_t v = (int64_t)bcast64((uint64_t)q->env[i]);
-        if (v < 0 || v >= nv) continue;
-        WSYNC();
-        const uint32_t st = rollout_env<MAXN, true, 0, false, TIER_SPILL, WS, WsSerialBig<MAXN>>(P, a, w, lane, v, lists);
-        note_status(P, lane, st);
-        done++;
-    }
-    if (lane == 0) {
-        if (done) atomicAdd(&q->total, (unsigned long long)done);
-        __threadfence();
-        if (atomicAdd(&q->done, 1u) == gridDim.x - 1) { q->count = 0u; q->done = 0u; }   // the last wave empties the queue
-    }
+    spill_drain<MAXN>(P, a.n * a.samples, [&](Ws<MAXN, false> &w, int lane, int64_t v, WsSerialBig<MAXN> *lists) {
+        return rollout_env<MAXN, true, 0, false, TIER_SPILL, Ws<MAXN, false>, WsSerialBig<MAXN>>(P, a, w, lane, v, lists);
+    });
 }

@@ -1,7 +1,8 @@
 """Per-kernel register / scratch / occupancy table of libtmg's translation
 units, from the compiler's kernel-resource-usage remarks (diagnostics).
 
-    python tools/resource_usage.py [EXTRA_HIPCC_FLAGS ...]     (TMG_TUS="4 5": those units only)
+    python tools/resource_usage.py [EXTRA_HIPCC_FLAGS ...]     (TMG_TUS="4 5": those units only; by default
+                                                                 every unit the Makefile lists)
 """
 import os
 import re
@@ -24,10 +25,16 @@ def short(name):
     return base + "<" + ",".join(("true" if v == "1" else "false") if t == "b" else v for t, v in args) + ">"
 
 
+def makefile_tus():
+    """The translation units of libtmg: the Makefile's TUS."""
+    with open(os.path.join(PKG, "Makefile")) as f:
+        return re.search(r"^TUS\s*=\s*(.*)$", f.read(), re.M).group(1).split()
+
+
 def main():
     extra = sys.argv[1:]
     rows = []
-    tus = [int(t) for t in os.environ.get("TMG_TUS", "1 2 3 4 5 6 7").split()]
+    tus = [int(t) for t in os.environ.get("TMG_TUS", " ".join(makefile_tus())).split()]
     with tempfile.TemporaryDirectory() as tmp:          # the translation units compile in parallel
         procs = [(tu, subprocess.Popen(["/opt/rocm/bin/hipcc", *FLAGS, *extra, f"-DTMG_TU={tu}", "-o",
                                         os.path.join(tmp, f"k{tu}.o"), "csrc/tmg_kernels.hip"], cwd=PKG,

@@ -153,6 +153,8 @@ enum : int {
     CV_ROLL_HORIZON,     // tmg_rollout: a rollout ended before `depth` because of the timer
     CV_ROLL_SPILL,       // tmg_rollout: virtual env queued for rollout_spill_kernel
     CV_ROLL_SPILL_RUN,   // tmg_rollout: virtual env re-run by rollout_spill_kernel
+    CV_BP_PAIR_ACC,      // bp_redraw_pairs: the round's second redraw taken from a guessed lane group
+    CV_BP_PAIR_REJ,      // bp_redraw_pairs: no lane group had guessed the second redraw's rows
     CV_COUNT = 48
 };
 #if TMG_COVER
@@ -1586,7 +1588,9 @@ __device__ __forceinline__ bool bp_rejected(const Params &P, const BpRing &r) {
 // redraw loop keeps fewer than N + 128 <= 640 colours filled ahead), so s = A^{-64m} X - A^{-64m}
 // G_{64m} inc (jump-table row 63 + m).
 // Colours filled ahead of the consume position: bp_prefetch fills while fewer
-// than maxM <= N <= 512 (C <= 32, N <= 512) are ahead, 128 at a time.
+// than maxM <= N <= 512 (C <= 32, N <= 512) are ahead, 128 at a time, and
+// bp_redraw_pairs while fewer than 2 N <= 256 are (N <= 128, bp_pair_shape):
+// fewer than 512 + 128 either way, well inside the ring's 1024.
 constexpr int kBpMaxAhead = 512 + 128;
 static_assert(kBpMaxAhead / 128 + 1 <= kJumpRows - 64,
               "bp_ring_state's backward jump needs a jump-table row for every batch count the ring can reach");
@@ -1612,13 +1616,14 @@ __device__ __forceinline__ void bp_ring_state(const Params &P, const BpJump &J, 
 // line search that decides the rows: bp_prefetch keeps at least maxM colours
 // filled ahead and issues every plane's two ring dwords, bp_apply merges rows
 // 0..row once the search has returned.  The LDS latency then overlaps the
-// search instead of following it.
+// search instead of following it.  rl: the board row this lane holds (the lane
+// itself, or the lane within its 16-lane group in bp_redraw_pairs' layout).
 template <int NB>
 struct BpReads {
     uint32_t lo[NB], hi[NB], sh;
 };
 template <int NB, class WS>
-__device__ __forceinline__ BpReads<NB> bp_prefetch(const Params &P, WS &w, int lane, BpJump &J, BpRing &r, int maxM) {
+__device__ __forceinline__ BpReads<NB> bp_prefetch(const Params &P, WS &w, int lane, int rl, BpJump &J, BpRing &r, int maxM) {
     r.fill = __builtin_amdgcn_readfirstlane(r.fill);
     r.cons = __builtin_amdgcn_readfirstlane(r.cons);
     while (r.fill - r.cons < maxM) bp_ring_fill<NB>(P, w, lane, J, r);
@@ -1627,7 +1632,7 @@ __device__ __forceinline__ BpReads<NB> bp_prefetch(const Params &P, WS &w, int l
     // for those stores to complete, so a compiler-only fence, not WSYNC's wait
     WFENCE();
     const uint32_t *ring = bp_ring(w);
-    const int o = r.cons + lane * P.C;
+    const int o = r.cons + rl * P.C;
     const int d = (o >> 5) & (kBpRingDw - 1);
     BpReads<NB> x;
     x.sh = (uint32_t)o & 31u;
@@ -1639,9 +1644,9 @@ __device__ __forceinline__ BpReads<NB> bp_prefetch(const Params &P, WS &w, int l
     return x;
 }
 template <int NB>
-__device__ __forceinline__ void bp_apply(const Params &P, int lane, BpRing &r, const BpReads<NB> &x, int row, uint32_t cm,
+__device__ __forceinline__ void bp_apply(const Params &P, int rl, BpRing &r, const BpReads<NB> &x, int row, uint32_t cm,
                                          RowPlanes<NB> &pl) {
-    const uint32_t in = lane <= row ? cm : 0u;
+    const uint32_t in = rl <= row ? cm : 0u;
 #pragma unroll
     for (int b = 0; b < NB; b++) {
         const uint32_t v = __builtin_amdgcn_alignbit(x.hi[b], x.lo[b], x.sh);
@@ -1652,10 +1657,10 @@ __device__ __forceinline__ void bp_apply(const Params &P, int lane, BpRing &r, c
 
 // rows 0..row <- the ring's next (row + 1) * C colours (colour plane only)
 template <int NB, class WS>
-__device__ __forceinline__ void bp_take(const Params &P, WS &w, int lane, BpJump &J, BpRing &r, int row,
+__device__ __forceinline__ void bp_take(const Params &P, WS &w, int lane, int rl, BpJump &J, BpRing &r, int row,
                                         uint32_t cm, RowPlanes<NB> &pl) {
-    const BpReads<NB> x = bp_prefetch<NB>(P, w, lane, J, r, (row + 1) * P.C);
-    bp_apply<NB>(P, lane, r, x, row, cm, pl);
+    const BpReads<NB> x = bp_prefetch<NB>(P, w, lane, rl, J, r, (row + 1) * P.C);
+    bp_apply<NB>(P, rl, r, x, row, cm, pl);
 }
 
 // The row of the first coord of the first line get_colour_lines would return
@@ -1686,6 +1691,161 @@ __device__ __forceinline__ int bp_first_line_row(const RowPlanes<NB> &pl, uint32
     return 63 - __clzll((~m & low) | 1ULL);                       // vertical: the top of its run
 }
 
+// ---------------------------------------------- two redraws per search round
+// A board of R <= 16 rows needs one 16-lane DPP row of the wave, so the other
+// three can search boards that may come next.  The board is held identically
+// in all four lane groups (lane 16g + r: row r), and since the redraw after
+// the one being applied (rows 0..rho) takes its colours from cons + (rho+1)C
+// whatever rows it redraws, only its row count rho' is unknown: group g =
+// 1..3 applies it with the guess rho' = rho + g - 2 on top of redraw 1, group
+// 0 applies redraw 1 alone, and one line search covers the four boards.
+// Group 0's result is the real rho'; if a group guessed it, that group's
+// board is exactly the board after redraw 2 and its result is rho'' (or the
+// end): two redraws for one search.  Otherwise redraw 2 is dropped and the
+// next round starts from rho'.  A guess outside [0, R-1] can never equal a
+// rho' and goes unused, so nothing is clipped.  The colours consumed and their
+// order are those of the one-redraw loop: a guess is only taken once the real
+// search has confirmed it.
+//
+// The guesses {rho-1, rho, rho+1}: on 10x10 boards of 4 colours rho' - rho is
+// 0 in 32 % of the redraws, +1 in 29 % and -1 in 18 % (the host emulator's
+// counts, tests/test_bp_pair_emulated.py, give the accepted share).
+//
+// TMG_BP_PAIR: A/B switch.  0: the one-redraw loop for every shape.  1 (the
+// library): the paired loop in the kernels specialised for one shape
+// (FIXED, from assume_shape's kernels: R and C are constants there), the one-redraw
+// loop in the generic ones, whose object code then is what it was: with both
+// loops in them their plain steps, which regenerate nothing, measured 2.5 %
+// slower and the 10x10 k5 line 1.3 %.  2 (the host wave
+// emulator): the paired loop for every shape of the predicate.  The 128-cell
+// kernels only, and boards of up to three planes: with four (k >= 9) the
+// round's second set of colours took the generic lean step kernels from 28 to
+// 32 bytes of scratch.
+#ifndef TMG_BP_PAIR
+#define TMG_BP_PAIR 1
+#endif
+template <class WS, int NB, bool FIXED>
+__device__ __forceinline__ bool bp_pair_shape(const Params &P) {
+    return (TMG_BP_PAIR == 2 || (TMG_BP_PAIR == 1 && FIXED)) && WS::NP <= 2 && NB <= 3 && P.R <= 16 && P.N <= 128 &&
+           P.C <= 32;
+}
+
+// The line search of bp_first_line_row on four boards at once: the row shifts
+// stay inside the lane's 16-lane group (row_shr:1, zero fill), and the row
+// ballot holds group g's rows in bits 16g..16g+15.
+struct BpLines {
+    uint32_t any, v, eqU;                        // per lane: anchors of the row, vertical ones, row == row above
+    uint64_t rows;                               // lanes holding an anchor
+};
+template <int NB>
+__device__ __forceinline__ BpLines bp_search_groups(const RowPlanes<NB> &pl, uint32_t hml, uint32_t vml) {
+    uint32_t neR = 0, neU = 0;
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const uint32_t x = pl.p[b];
+        neR |= x ^ (x >> 1);
+        neU |= x ^ (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);   // row_shr:1: row r-1
+    }
+    BpLines s;
+    s.eqU = ~neU;
+    const uint32_t h = ~(neR | (neR >> 1)) & hml;
+    s.v = s.eqU & (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s.eqU, 0x111, 0xf, 0xf, true) & vml;
+    s.any = h | s.v;
+    s.rows = __ballot(s.any != 0u);
+    return s;
+}
+// group g's first line: its first coord's row, or -1 (bp_first_line_row's rule)
+__device__ __forceinline__ int bp_group_line_row(const BpLines &s, int g) {
+    const int sh = 16 * g;
+    const uint32_t rows = (uint32_t)(s.rows >> sh) & 0xffffu;
+    if (!rows) return -1;
+    const int rs = 31 - __builtin_clz(rows);                     // bottom-most row holding a line
+    const uint32_t av = (uint32_t)__builtin_amdgcn_readlane((int)s.any, sh + rs);
+    const uint32_t vv = (uint32_t)__builtin_amdgcn_readlane((int)s.v, sh + rs);
+    const int c0 = __builtin_ctz(av);                            // leftmost line, vertical checked first
+    if (!((vv >> c0) & 1u)) return rs;                           // horizontal: starts at (rs, c0)
+    const uint32_t m = (uint32_t)(__ballot((s.eqU & (1u << c0)) != 0u) >> sh);   // (r, c0) == (r-1, c0)
+    const uint32_t low = (2u << rs) - 1u;
+    return 31 - __builtin_clz((~m & low) | 1u);                  // vertical: the top of its run
+}
+
+// bits of v where m is set, bits of old elsewhere: one v_bfi_b32 (the compiler
+// lowers the C form to a v_not and three more wherever old has a second use)
+__device__ __forceinline__ uint32_t bp_merge(uint32_t m, uint32_t v, uint32_t old) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(v), "v"(old));
+    return r;
+#else
+    return (v & m) | (old & ~m);
+#endif
+}
+
+// remove_colour_lines' redraws (board.py:120-131), two per round where a guess
+// holds.  pl: the board, the same in every lane group, on entry and on return.
+template <int NB, class WS>
+__device__ __forceinline__ void bp_redraw_pairs(const Params &P, WS &w, int lane, BpJump &J, BpRing &r, uint32_t cm,
+                                                RowPlanes<NB> &pl) {
+    const int R = P.R, C = P.C;
+    // lane-derived constants of this loop only (an opaque lane: not computed
+    // at the kernel's start and held through the move's cascade)
+    const int ll = loop_lane(lane);
+    const int rl = ll & 15, grp = ll >> 4;
+    const uint32_t hml = (rl < R && C >= 3) ? cm >> 2 : 0u;           // columns <= C-3
+    const uint32_t vml = (rl >= 2 && rl < R) ? cm : 0u;               // rows >= 2
+    // Rows as colour offsets: row rl is in a redraw of rows 0..row iff rlC <
+    // (row + 1) C; the group's guess rho + grp - 2 reaches it iff glC < (rho + 1) C
+    const int rlC = rl * C;
+    const int glC = grp ? (rl + 2 - grp) * C : 0x10000;
+    const int ahead = 2 * P.N;                                         // both redraws' colours, <= 256
+    const uint32_t *ring = bp_ring(w);
+    // the ring's counters said uniform once, here: through the rounds they then stay in SGPRs
+    r.fill = __builtin_amdgcn_readfirstlane(r.fill);
+    r.cons = __builtin_amdgcn_readfirstlane(r.cons);
+    int r0 = bp_group_line_row(bp_search_groups<NB>(pl, hml, vml), 0);
+    while (r0 >= 0) {
+        const int row = R - 1 < r0 + 1 ? R - 1 : r0 + 1;              // redraw 1: rows 0..row (rho)
+        const int s1 = (row + 1) * C;
+        while (r.fill - r.cons < ahead) bp_ring_fill<NB>(P, w, lane, J, r);
+        WFENCE();                                                      // as bp_prefetch
+        const int o1 = r.cons + rlC, o2 = o1 + s1;
+        const int d1 = (o1 >> 5) & (kBpRingDw - 1), d2 = (o2 >> 5) & (kBpRingDw - 1);
+        uint32_t lo1[NB], hi1[NB], lo2[NB], hi2[NB];
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            lo1[b] = ring[b * kBpPlaneDw + d1];
+            hi1[b] = ring[b * kBpPlaneDw + d1 + 1];
+            lo2[b] = ring[b * kBpPlaneDw + d2];
+            hi2[b] = ring[b * kBpPlaneDw + d2 + 1];
+        }
+        const uint32_t in1 = rlC < s1 ? cm : 0u;
+        const uint32_t in2 = glC < s1 ? cm : 0u;
+        RowPlanes<NB> pg;                                              // redraw 1, then this group's guess
+        uint32_t v2[NB];
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const uint32_t v1 = __builtin_amdgcn_alignbit(hi1[b], lo1[b], (uint32_t)o1 & 31u);
+            v2[b] = __builtin_amdgcn_alignbit(hi2[b], lo2[b], (uint32_t)o2 & 31u);
+            pl.p[b] = bp_merge(in1, v1, pl.p[b]);
+            pg.p[b] = bp_merge(in2, v2[b], pl.p[b]);
+        }
+        r.cons += s1;
+        const BpLines s = bp_search_groups<NB>(pg, hml, vml);
+        r0 = bp_group_line_row(s, 0);
+        if (r0 < 0) break;
+        const int row2 = R - 1 < r0 + 1 ? R - 1 : r0 + 1;             // redraw 2: rows 0..row2 (rho')
+        const int g = row2 - row + 2;
+        if (g < 1 || g > 3) { COVER(CV_BP_PAIR_REJ); continue; }     // not guessed: redraw 2 opens the next round
+        COVER(CV_BP_PAIR_ACC);
+        r0 = bp_group_line_row(s, g);
+        const int s2 = (row2 + 1) * C;
+        const uint32_t inb = rlC < s2 ? cm : 0u;
+#pragma unroll
+        for (int b = 0; b < NB; b++) pl.p[b] = bp_merge(inb, v2[b], pl.p[b]);
+        r.cons += s2;
+    }
+}
+
 // the LDS colour plane from the row planes (cell p: row r's planes by bpermute)
 template <int NB, class WS>
 __device__ __forceinline__ void bp_to_lds(const Params &P, WS &w, int lane, const RowPlanes<NB> &pl) {
@@ -1702,15 +1862,15 @@ __device__ __forceinline__ void bp_to_lds(const Params &P, WS &w, int lane, cons
     }
 }
 
-// the row planes from the LDS colour plane (after a shuffle)
+// the row planes from the LDS colour plane (after a shuffle): row rl on this lane
 template <int NB, class WS>
-__device__ __forceinline__ RowPlanes<NB> bp_from_lds(const Params &P, const WS &w, int lane) {
+__device__ __forceinline__ RowPlanes<NB> bp_from_lds(const Params &P, const WS &w, int rl) {
     RowPlanes<NB> pl;
 #pragma unroll
     for (int b = 0; b < NB; b++) pl.p[b] = 0;
-    const int r = lane < P.R ? lane : 0;
+    const int r = rl < P.R ? rl : 0;
     for (int c = 0; c < P.C; c++) {
-        const uint32_t x = lane < P.R ? (uint32_t)(w.brd[r * P.C + c] - 1) : 0u;
+        const uint32_t x = rl < P.R ? (uint32_t)(w.brd[r * P.C + c] - 1) : 0u;
 #pragma unroll
         for (int b = 0; b < NB; b++) pl.p[b] |= ((x >> b) & 1u) << c;
     }
@@ -1728,7 +1888,7 @@ __device__ __forceinline__ RowPlanes<NB> bp_from_lds(const Params &P, const WS &
 // one wave, while the other streams' steps share its SIMD (measured: the lean
 // kernels' inline autoreset and the 512-cell reset kernel gain; the 128-cell
 // masked reset, beside the c3 step kernels, loses 0.6 %: not raised there).
-template <int NB, bool PRIO = true, class WS>
+template <int NB, bool PRIO = true, bool FIXED = false, class WS>
 __device__ __forceinline__ int bp_generate(const Params &P, WS &w, int lane, Rng &g) {
     const int R = P.R, C = P.C, N = P.N;
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
@@ -1747,7 +1907,10 @@ __device__ __forceinline__ int bp_generate(const Params &P, WS &w, int lane, Rng
     RowPlanes<NB> pl;
 #pragma unroll
     for (int b = 0; b < NB; b++) pl.p[b] = 0;
-    bp_take<NB>(P, w, lane, J, r, R - 1, cm, pl);                       // :97
+    // bp_redraw_pairs' shapes hold the board in every 16-lane group
+    const bool pair = bp_pair_shape<WS, NB, FIXED>(P);
+    const int rl = pair ? (loop_lane(lane) & 15) : lane;
+    bp_take<NB>(P, w, lane, rl, J, r, R - 1, cm, pl);                   // :97
     int fl = 0;
     bool rej = false;
     for (int shuffles = 0;; shuffles++) {
@@ -1755,8 +1918,9 @@ __device__ __forceinline__ int bp_generate(const Params &P, WS &w, int lane, Rng
         // once the redraws end: until then the colours of a stream with a
         // rejected word are still colours, the loop ends as it would on any
         // other board, and the board is then redone exactly.
-        for (;;) {
-            const BpReads<NB> x = bp_prefetch<NB>(P, w, lane, J, r, N);          // the next redraw's colours
+        if (pair) bp_redraw_pairs<NB>(P, w, lane, J, r, cm, pl);
+        else for (;;) {
+            const BpReads<NB> x = bp_prefetch<NB>(P, w, lane, lane, J, r, N);    // the next redraw's colours
             const int r0 = bp_first_line_row<NB>(pl, hml, vml);
             if (r0 < 0) break;
             bp_apply<NB>(P, lane, r, x, R - 1 < r0 + 1 ? R - 1 : r0 + 1, cm, pl);   // rows 0..min(R-1, r0+1)
@@ -1772,7 +1936,7 @@ __device__ __forceinline__ int bp_generate(const Params &P, WS &w, int lane, Rng
         bp_ring_state(P, J, r, g);                                       // shuffle draws from the stream itself
         WSYNC();
         shuffle(P, w, lane, g);                                          // :105-106
-        pl = bp_from_lds<NB>(P, w, lane);
+        pl = bp_from_lds<NB>(P, w, rl);
         fl = FL_SHUF;
         bp_ring_init<NB>(P, w, lane, g, r, J);
     }
@@ -2648,7 +2812,7 @@ __device__ __forceinline__ void store_rng(uint64_t *p, const Rng &g, int lane) {
 //      stepping (its action ignored, reward 0, not terminated).
 // Returns the ST_* bits this step raises for the sticky status word.
 template <int MAXN, bool GEN, int SBNB, bool CODD, int TIER = TIER_MAIN, class WS = Ws<MAXN, GEN>,
-          class L = WsSerial<MAXN>>
+          class L = WsSerial<MAXN>, bool FIXED = false>
 __device__ __forceinline__ uint32_t step_env(
     const Params &P, WS &w, int lane, int64_t e, int8_t *__restrict__ board, uint64_t *__restrict__ rng, int32_t *__restrict__ timer,
     const int32_t *__restrict__ actions, int32_t *__restrict__ reward, int32_t *__restrict__ n_new,
@@ -2836,7 +3000,7 @@ __device__ __forceinline__ uint32_t step_env(
             if (regen_inline) {
                 int fg = -1;
                 if constexpr (SBNB > 0) {
-                    if (P.C <= 32) fg = bp_generate<SBNB>(P, w, lane, g);
+                    if (P.C <= 32) fg = bp_generate<SBNB, true, FIXED>(P, w, lane, g);
                     if (fg < 0) {
                         if (rowp) J = load_jump(P, lane, g);
                         fg = sb_generate_exact<SBNB, CODD>(P, w, lane, J, g, cl);
@@ -2963,7 +3127,7 @@ __global__ __launch_bounds__(64, MAXN == 128 ? (GEN ? kGen128Waves : (FIX != kNo
     if (e >= n) return;
     WsSerial<MAXN> *lists = nullptr;
     if constexpr (GEN) lists = &w.s;
-    const uint32_t st = step_env<MAXN, GEN, SBNB, CODD, TIER_MAIN, WS, WsSerial<MAXN>>(
+    const uint32_t st = step_env<MAXN, GEN, SBNB, CODD, TIER_MAIN, WS, WsSerial<MAXN>, FIX != kNoFix>(
         P, w, lane, e, board, rng, timer, actions, reward, n_new, n_act, flags_out, eff, trust_eff, autoreset, lists);
     note_status(P, lane, st);
 }
@@ -3019,7 +3183,7 @@ __global__ __launch_bounds__(64, 8) void spill_kernel(
 }
 
 // TileMatchEnv.reset without a seed (tile_match_env.py:84-91) of env e
-template <int MAXN, int SBNB, bool CODD, class WS>
+template <int MAXN, int SBNB, bool CODD, bool FIXED = false, class WS>
 __device__ __forceinline__ void reset_env(const Params &P, WS &w, int lane, int64_t e, int8_t *__restrict__ board,
                                           uint64_t *__restrict__ rng, int32_t *__restrict__ timer,
                                           uint64_t *__restrict__ eff) {
@@ -3030,7 +3194,7 @@ __device__ __forceinline__ void reset_env(const Params &P, WS &w, int lane, int6
     // wider board takes the exact draw-by-draw path
     int fl = -1;
     if constexpr (SBNB > 0) {
-        if (P.C <= 32) fl = bp_generate<SBNB, (MAXN > 128)>(P, w, lane, g);
+        if (P.C <= 32) fl = bp_generate<SBNB, (MAXN > 128), FIXED>(P, w, lane, g);
     }
     if (fl < 0) {
         const LaneJump J = load_jump(P, lane, g);
@@ -3072,7 +3236,7 @@ __global__ __launch_bounds__(64, MAXN > 128 ? kReset512Waves : (FIX != kNoFix ? 
     while (todo) {
         const int k = __builtin_ctzll(todo);
         todo &= todo - 1;
-        reset_env<MAXN, SBNB, CODD>(P, w, loop_lane(lane), e0 + k, board, rng, timer, eff);
+        reset_env<MAXN, SBNB, CODD, FIX != kNoFix>(P, w, loop_lane(lane), e0 + k, board, rng, timer, eff);
         WSYNC();                                                         // the next board reuses the workspace
     }
 }

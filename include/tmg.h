@@ -186,6 +186,65 @@ TMG_API int tmg_rollout(tmg_ctx *ctx, int64_t n, const int8_t *board,
                         int32_t *best_total,      /* [n] that total, or NULL */
                         void *stream);
 
+/* Successor states of every effective action: the expansion step of a tree
+ * search that keeps its children (board, RNG position, timer, mask), to peek,
+ * roll out, expand again or score them.  Two calls: tmg_expand_count places
+ * the children, tmg_expand writes and steps them.
+ *
+ * tmg_expand_count: first_child[i] = number of children of envs 0..i-1 (an
+ * exclusive prefix sum), first_child[n] = the total.  Env i has one child per
+ * action a in [0, A) whose bit is set in eff[i] (and in select[i], when select
+ * != NULL); bits at or above A are ignored; an env with timer[i] >= num_moves
+ * has none, whatever its mask.  Computed on the device with no host round
+ * trip, deterministically, for any n up to 2^31.  n == 0 writes first_child[0]
+ * = 0.  Refused: a tmg_create_scan context, negative n, a null first_child, a
+ * null timer or eff with n > 0. */
+TMG_API int tmg_expand_count(tmg_ctx *ctx, int64_t n, const int32_t *timer, const uint64_t *eff,
+                             const uint64_t *select /* [n][W] or NULL */,
+                             int64_t *first_child /* [n+1], device */, void *stream);
+
+/* tmg_expand: child row c = first_child[i] + (rank of a among env i's expanded
+ * actions, ascending) becomes exactly what tmg_step(actions = a, autoreset = 0)
+ * leaves and reports on a copy of env i whose RNG words are rng[i].
+ *   The child: row c of child_board / child_rng / child_timer / child_eff is
+ *     the state after the move (Board.move, board.py:330-395; child_timer =
+ *     timer[i] + 1), row c of child_reward / child_n_new / child_n_act /
+ *     child_flags what the move reports.  A child that reaches num_moves
+ *     carries TMG_FLAG_DONE and an all-zero mask (tile_match_env.py:119-120).
+ *     child_parent[c] = i (optional), child_action[c] = a.  Children are
+ *     ordered env-major, then by ascending action.  Nothing of board, rng,
+ *     timer, eff, select or first_child is written.
+ *   rng: as tmg_peek.  The envs' own array gives the children the env would
+ *     really reach; any other [n][5] array of PCG64 words gives sampled
+ *     children.
+ *   trust_eff: as tmg_step.  Non-zero: eff is this library's mask of these
+ *     boards.  Zero: the boards were edited by hand, eff is the mask
+ *     tmg_effective wrote for them, and the general kernels run.  eff is
+ *     required either way: it names the children.  A child of an action that
+ *     turns out ineffective is what a step of it is: reward 0, board
+ *     unchanged, timer + 1.
+ *   m: the number of child rows to produce, known to the host (the caller
+ *     reads first_child[n] after tmg_expand_count).  m below the total expands
+ *     the first m rows only, a prefix; rows from m on are not touched.  For m
+ *     above the total the excess rows get child_timer = num_moves,
+ *     child_action = 0, child_parent = -1 and a zero mask, and the step treats
+ *     them as steps after done: TMG_FLAG_ERROR, board and RNG words untouched,
+ *     TMG_STATUS_CALLER.  No kernel runs on rows nobody initialised.
+ *   The moves are a tmg_step of the m rows, routed as any step (the
+ *     lane-per-board, shape-specialised or generic kernels); steps that
+ *     outgrow the LDS lists go through the spill tier and count in tmg_spills.
+ *   Refused: a tmg_create_scan context, negative n or m, n or m above 2^26 - 8
+ *     (one wave each), a null required pointer, a child_board that is not
+ *     8-byte aligned (the lane-per-board step reads boards as 8-byte words).
+ *     n == 0 or m == 0 is a no-op.  Asynchronous on `stream`. */
+TMG_API int tmg_expand(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, const int32_t *timer,
+                       const uint64_t *eff, const uint64_t *select, int trust_eff,
+                       const int64_t *first_child, int64_t m,
+                       int8_t *child_board, uint64_t *child_rng, int32_t *child_timer, uint64_t *child_eff,
+                       int64_t *child_parent /* or NULL */, int32_t *child_action,
+                       int32_t *child_reward, int32_t *child_n_new, int32_t *child_n_act, uint8_t *child_flags,
+                       void *stream);
+
 /* Step plans: one host call per batched step of a fixed set of buffers
  * (TileMatchEnv.step, tile_match_env.py:93-124, for every env of the batch),
  * with the batch split into env groups on their own streams, the callers'

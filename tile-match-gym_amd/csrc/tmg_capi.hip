@@ -15,6 +15,7 @@
 #include "tmg.h"
 #include "tmg_board.hip"
 #include "tmg_dispatch.h"
+#include "tmg_expand.hip"
 #include "tmg_launch.h"
 #include "tmg_seed.h"
 
@@ -551,6 +552,52 @@ int tmg_rollout(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rn
     return hip_check(hipGetLastError(), "kernel launch");
 }
 
+// one wave per env (or child row): the padded grid's threads must stay below 2^32
+static constexpr int64_t kMaxWaveRows = (1LL << 26) - 8;
+
+int tmg_expand_count(tmg_ctx *ctx, int64_t n, const int32_t *timer, const uint64_t *eff, const uint64_t *select,
+                     int64_t *first_child, void *stream) {
+    int rc = check_full(ctx, n);
+    if (rc) return rc;
+    if (n > (1LL << 31)) return fail(-2, "more than 2^31 envs");
+    if (!first_child) return fail(-1, "null first_child");
+    if (n > 0 && (!timer || !eff)) return fail(-1, "null state buffer");
+    const Params &P = ctx->P;
+    const tmg::ExpandCountArgs a{n, P.W, P.A, P.num_moves, timer, eff, select, first_child};
+    tmg::launch_expand_count(reinterpret_cast<hipStream_t>(stream), a);
+    return hip_check(hipGetLastError(), "kernel launch");
+}
+
+int tmg_expand(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, const int32_t *timer,
+               const uint64_t *eff, const uint64_t *select, int trust_eff, const int64_t *first_child, int64_t m,
+               int8_t *child_board, uint64_t *child_rng, int32_t *child_timer, uint64_t *child_eff,
+               int64_t *child_parent, int32_t *child_action, int32_t *child_reward, int32_t *child_n_new,
+               int32_t *child_n_act, uint8_t *child_flags, void *stream) {
+    int rc = check_full(ctx, n);
+    if (rc) return rc;
+    if (m < 0) return fail(-2, "negative child count");
+    if (n > kMaxWaveRows || m > kMaxWaveRows) return fail(-2, "n or m is more than one launch holds (2^26 - 8 waves)");
+    if (n == 0 || m == 0) return 0;
+    if (!board || !rng || !timer || !eff || !first_child) return fail(-1, "null state buffer");
+    if (!child_board || !child_rng || !child_timer || !child_eff || !child_action || !child_reward || !child_n_new ||
+        !child_n_act || !child_flags)
+        return fail(-1, "null child buffer");
+    // the lane-per-board step reads boards as 8-byte words (tmg_lane.h), and
+    // the gather writes them as dwords / 2-byte halves
+    if (reinterpret_cast<uintptr_t>(child_board) & 7) return fail(-2, "child_board must be 8-byte aligned");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const Params &P = ctx->P;
+    const tmg::ExpandArgs g{n, m, P.N, P.W, P.A, P.num_moves, board, rng, timer, eff, select, first_child,
+                            child_board, child_rng, child_timer, child_eff, child_parent, child_action};
+    tmg::launch_expand_gather(ctx->maxn, s, g);
+    rc = hip_check(hipGetLastError(), "kernel launch");
+    if (rc) return rc;
+    // the moves: a step of the m rows, routed as any step (route_step)
+    const StepArgs a{m, child_board, child_rng, child_timer, child_action, child_reward, child_n_new, child_n_act,
+                     child_flags, child_eff, trust_eff ? 1 : 0, 0};
+    return do_step(ctx, P, a, s);
+}
+
 // ------------------------------------------------------------- step plans
 struct tmg_plan {
     tmg_ctx *ctx;
@@ -861,7 +908,7 @@ __attribute__((visibility("default"))) int tmg_debug_cover(tmg_ctx *ctx, uint64_
 int tmg_num_actions(const tmg_ctx *ctx) { return ctx ? ctx->P.A : -1; }
 int tmg_mask_words(const tmg_ctx *ctx) { return ctx ? ctx->P.W : -1; }
 const char *tmg_last_error(void) { return g_err.c_str(); }
-int tmg_abi_version(void) { return 7; }
+int tmg_abi_version(void) { return 8; }
 const char *tmg_build_info(void) { return "src=" TMG_SRC_SHA ";variant=" TMG_VARIANT; }
 
 }  // extern "C"

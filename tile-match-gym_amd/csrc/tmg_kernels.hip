@@ -1,5 +1,5 @@
 // tmg_kernels.hip — kernel instantiations and their host launchers
-// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..11, so the
+// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..12, so the
 // heavy template instantiations build in parallel; each TU registers only its
 // own kernels.
 #include <hip/hip_runtime.h>
@@ -22,8 +22,12 @@
 #include "tmg_aux.hip"      // non-template kernels: one TU only
 #endif
 
+#if TMG_TU == 12
+#include "tmg_expand.hip"   // tmg_expand's count / scan and gather kernels
+#endif
+
 #ifndef TMG_TU
-#error "compile tmg_kernels.hip with -DTMG_TU=1..11"
+#error "compile tmg_kernels.hip with -DTMG_TU=1..12"
 #endif
 
 namespace tmg {
@@ -139,6 +143,20 @@ void launch_rollout_spill512(hipStream_t s, const Params &P, const RollArgs &a) 
 void launch_rollout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const RollArgs &a) {
     RollLaunch l{grid, s, P, a};
     peek_gen_ladder(P, maxn, sb, l);
+}
+#endif
+
+#if TMG_TU == 12
+void launch_expand_count(hipStream_t s, const ExpandCountArgs &a) {
+    const unsigned tiles = (unsigned)((a.n + kExpandTile - 1) / kExpandTile);
+    if (tiles) hipLaunchKernelGGL(expand_count_kernel<0>, dim3(tiles), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(expand_count_kernel<1>, dim3(1), dim3(64), 0, s, a);
+    if (tiles) hipLaunchKernelGGL(expand_count_kernel<2>, dim3(tiles), dim3(64), 0, s, a);
+}
+void launch_expand_gather(int maxn, hipStream_t s, const ExpandArgs &a) {
+    const dim3 grid = env_grid(a.n);
+    if (maxn == 128) hipLaunchKernelGGL((expand_gather_kernel<1, kExpandPack>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((expand_gather_kernel<4, kExpandPack>), grid, dim3(64), 0, s, a);
 }
 #endif
 

@@ -93,6 +93,16 @@ void launch_rollout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Param
 void launch_rollout_reduce(hipStream_t s, int64_t n, int A, int samples, const int32_t *ret, int32_t *total,
                            int32_t *best_action, int32_t *best_total);
 
+// tmg_expand_count / tmg_expand (tmg_expand.hip): the child rows of every
+// effective action, counted and placed on the device; the moves themselves
+// are a step launch on those rows (tmg_capi.hip)
+struct ExpandCountArgs;
+struct ExpandArgs;
+// TU 12 — the count / scan launches (n == 0: first_child[0] = 0 only) and the
+// gather, one wave per parent env
+void launch_expand_count(hipStream_t s, const ExpandCountArgs &a);
+void launch_expand_gather(int maxn, hipStream_t s, const ExpandArgs &a);
+
 // bytes of one spill-kernel wave's worst-case global-memory lists
 size_t spill_ws_bytes(int maxn);
 

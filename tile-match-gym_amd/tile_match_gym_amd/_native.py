@@ -26,9 +26,9 @@ EXPORTS = ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_ste
            "tmg_onehot", "tmg_onehot_channels", "tmg_count_states", "tmg_sample_effective", "tmg_status",
            "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot", "tmg_plan_create", "tmg_plan_config",
            "tmg_plan_step", "tmg_plan_join", "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch",
-           "tmg_graph_destroy", "tmg_peek", "tmg_rollout", "tmg_seed")
+           "tmg_graph_destroy", "tmg_peek", "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand")
 DTYPE_F32, DTYPE_U8, DTYPE_I32 = 0, 1, 2
-ABI_VERSION = 7
+ABI_VERSION = 8
 SEED_INT, SEED_SPAWN, SEED_STORE_DIRECT, SEED_STORE_STAGED = 0, 1, 0x100, 0x200
 STATUS_INTERNAL, STATUS_OVERFLOW, STATUS_CALLER = 1, 2, 4
 
@@ -104,12 +104,14 @@ def load(path: str = None):
     L.tmg_peek.argtypes = [P, I64, P, P, P, I, P, P, P, P, P, P, P]
     L.tmg_rollout.argtypes = [P, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32, P, P, P, P, P, P, P]
     L.tmg_seed.argtypes = [P, I64, I, P, I, U64, U64, U64, U64, I64, P, P]
+    L.tmg_expand_count.argtypes = [P, I64, P, P, P, P, P]
+    L.tmg_expand.argtypes = [P, I64, P, P, P, P, P, I, P, I64] + [P] * 10 + [P]
     for name in ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_step", "tmg_effective",
                  "tmg_num_actions", "tmg_mask_words", "tmg_abi_version", "tmg_onehot", "tmg_onehot_channels",
                  "tmg_sample_effective", "tmg_status", "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot",
                  "tmg_count_states", "tmg_plan_create", "tmg_plan_config", "tmg_plan_step", "tmg_plan_join",
                  "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy", "tmg_peek",
-                 "tmg_rollout", "tmg_seed"):
+                 "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand"):
         getattr(L, name).restype = I
     if L.tmg_abi_version() != ABI_VERSION:
         raise TmgError("libtmg.so ABI version mismatch; rebuild it")
@@ -219,6 +221,21 @@ class Context:
         self._check(self._L.tmg_rollout(self._h, int(n), board, rng, timer, eff, int(trust_eff), int(depth),
                                         int(samples), int(key) % 2 ** 64, int(first_env), int(t), ret, plies, flags,
                                         total, best_action, best_total, stream))
+
+    def expand_count(self, n, timer, eff, select, first_child, stream):
+        """tmg_expand_count: first_child ([n + 1] int64, device) <- the exclusive prefix sum of every env's
+        child count (its effective actions, of those in select ([n][W] words) when given; none for a
+        finished env), first_child[n] the total.  No host round trip."""
+        self._check(self._L.tmg_expand_count(self._h, int(n), timer, eff, select, first_child, stream))
+
+    def expand(self, n, board, rng, timer, eff, select, trust_eff, first_child, m, child_board, child_rng,
+               child_timer, child_eff, child_parent, child_action, child_reward, child_n_new, child_n_act,
+               child_flags, stream):
+        """tmg_expand: the m child rows first_child places, each what tmg_step(actions = a, autoreset = 0)
+        leaves and reports on a copy of its parent env (child_parent may be None).  No input is written."""
+        self._check(self._L.tmg_expand(self._h, int(n), board, rng, timer, eff, select, int(trust_eff), first_child,
+                                       int(m), child_board, child_rng, child_timer, child_eff, child_parent,
+                                       child_action, child_reward, child_n_new, child_n_act, child_flags, stream))
 
     def seed(self, m, rng, stream, mode=SEED_INT, seeds=None, seed_words=1, base=0, key0=0, key1=0, period=0):
         """tmg_seed: the PCG64 words of m streams into rng ([m][5] uint64), seeded on the device as numpy

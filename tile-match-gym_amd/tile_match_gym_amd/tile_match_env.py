@@ -430,6 +430,44 @@ class TileMatchEnv(_EnvBase):
         return {"ret": o[0], "plies": o[1], "is_combination_match": (f & _native.FLAG_COMBO) != 0,
                 "shuffled": (f & _native.FLAG_SHUFFLED) != 0}
 
+    def expand(self) -> dict:
+        """The states step(a) would lead to, for every effective action a,
+        without changing the env (tmg_expand on the host-side board, the mask
+        scanned from it, the env's own RNG stream and timer).  numpy arrays
+        with one row per child, by ascending action: action (int32), board
+        ((m, 2, R, C) int32, the observation's board), rng_words ((m, 5)
+        uint64, the stream position after the move), reward, num_new_specials,
+        num_specials_activated (int32), is_combination_match, shuffled, done
+        (bool).  A finished env has no child."""
+        if self.timer is None:
+            raise Exception("You must call reset before calling expand")
+        self._upload()
+        self._d_timer.fill_(self.timer)
+        s = self._stream()
+        self._ctx.effective(1, self._d_board.data_ptr(), self._d_eff.data_ptr(), s)
+        first = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self._ctx.expand_count(1, self._d_timer.data_ptr(), self._d_eff.data_ptr(), None, first.data_ptr(), s)
+        m = int(first[1].item())
+        kw = dict(device=self.device)
+        board = torch.zeros((m, 2, self.num_rows, self.num_cols), dtype=torch.int8, **kw)
+        rng = torch.zeros((m, 5), dtype=torch.int64, **kw)
+        timer = torch.zeros(m, dtype=torch.int32, **kw)
+        eff = torch.zeros((m, self._ctx.mask_words), dtype=torch.int64, **kw)
+        out = torch.zeros((4, m), dtype=torch.int32, **kw)          # action, reward, n_new, n_act
+        flags = torch.zeros(m, dtype=torch.uint8, **kw)
+        if m:
+            self._ctx.expand(1, self._d_board.data_ptr(), self._d_rng.data_ptr(), self._d_timer.data_ptr(),
+                             self._d_eff.data_ptr(), None, 0, first.data_ptr(), m, board.data_ptr(), rng.data_ptr(),
+                             timer.data_ptr(), eff.data_ptr(), None, out[0].data_ptr(), out[1].data_ptr(),
+                             out[2].data_ptr(), out[3].data_ptr(), flags.data_ptr(), s)
+        o, f = out.cpu().numpy(), flags.cpu().numpy()
+        if (f & (_native.FLAG_ERROR | _native.FLAG_OVERFLOW)).any():
+            raise _native.TmgError("device reported an error for an expanded move")
+        return {"action": o[0], "board": board.to(torch.int32).cpu().numpy(),
+                "rng_words": rng.cpu().numpy().view(np.uint64), "reward": o[1], "num_new_specials": o[2],
+                "num_specials_activated": o[3], "is_combination_match": (f & _native.FLAG_COMBO) != 0,
+                "shuffled": (f & _native.FLAG_SHUFFLED) != 0, "done": (f & _native.FLAG_DONE) != 0}
+
     def _get_obs(self):                                                       # tile_match_env.py:114-115
         return OrderedDict([("board", self.board.board.copy()), ("num_moves_left", self.num_moves - self.timer)])
 

@@ -65,6 +65,26 @@ if hasattr(torch._C, "_cuda_getCurrentRawStream"):
     _raw_stream = torch._C._cuda_getCurrentRawStream        # noqa: F811
 
 
+class Expansion:
+    """What TileMatchVecEnv.expand returns.  count: the number of child rows;
+    first_child: (N + 1,) int64, env i's children are rows first_child[i] to
+    first_child[i + 1] (first_child[N] is the total, which count is unless
+    max_children cut it); per child row: parent (int64, its env), action,
+    reward, n_new, n_act (int32) and flags (uint8), what the move reported (as
+    a step with autoreset off: FLAG_DONE on a child that used the last move);
+    env: a TileMatchVecEnv over the children's boards, RNG words, timers and
+    masks (None when count == 0), with the parent's shape, colours, specials and
+    num_moves, autoreset mode "none", the mask cache valid and no reset run, so
+    env.peek(), env.rollout(), env.step_raw() and env.expand() work on it
+    directly.  It shares the parent env's context: close the parent last."""
+
+    __slots__ = ("count", "first_child", "parent", "action", "reward", "n_new", "n_act", "flags", "env")
+
+    def __init__(self, count, first_child, parent, action, reward, n_new, n_act, flags, env):
+        self.count, self.first_child, self.parent, self.action = count, first_child, parent, action
+        self.reward, self.n_new, self.n_act, self.flags, self.env = reward, n_new, n_act, flags, env
+
+
 class TileMatchVecEnv:
     def __init__(self, num_envs: int, num_rows: int, num_cols: int, num_colours: int, num_moves: int,
                  colourless_specials=(), colour_specials=(), seed: int = 0, seeds=None, device=None,
@@ -485,6 +505,114 @@ class TileMatchVecEnv:
         self.step_raw(self.actions, fork=fork)
         return out["best_total"]
 
+    def expand(self, select=None, rng=None, max_children: int = None) -> "Expansion":
+        """The successor states of every effective action of every env, without
+        changing any state (tmg_expand_count + tmg_expand): one child per (env,
+        effective action), env-major and by ascending action, each exactly what
+        a step of that action (autoreset off) leaves and reports on a copy of
+        the env.  The children are an env of their own, Expansion.env, to peek,
+        roll out, step or expand again.
+        select: an (N, A) bool tensor; only the effective actions it names are
+        expanded (packed to mask words on the device).  rng as for peek: None
+        gives the children the envs would really reach, an (N, 5) int64 device
+        tensor of other PCG64 words sampled ones.  max_children: at most that
+        many rows, the first ones.  A finished env (autoreset off) has no child.
+        Joins, counts the children on the device, then reads the total: the one
+        host wait of the call, needed to allocate exactly that many rows."""
+        self.join()
+        N, A, W = self.num_envs, self.num_actions, self.mask_words
+        dev = self.board.device
+        if rng is None:
+            rng = self.rng
+        elif rng.shape != (N, 5) or rng.dtype != torch.int64 or rng.device != dev or not rng.is_contiguous():
+            raise ValueError(f"rng must be a contiguous ({N}, 5) int64 tensor on {dev}")
+        sel = None
+        if select is not None:
+            select = torch.as_tensor(select, device=dev)
+            if select.shape != (N, A) or select.dtype != torch.bool:
+                raise ValueError(f"select must be a ({N}, {A}) bool tensor")
+            bits = torch.zeros((N, W * 64), dtype=torch.int64, device=dev)
+            bits[:, :A] = select
+            sel = (bits.view(N, W, 64) << torch.arange(64, device=dev, dtype=torch.int64)).sum(dim=-1).contiguous()
+        if max_children is not None and int(max_children) < 0:
+            raise ValueError("max_children must be >= 0")
+        # a mask from tmg_effective (hand-edited boards) may sit beside a line
+        # on the board, so those moves run untrusted (tmg.h, trust_eff)
+        trust = int(self._eff_valid)
+        if not self._eff_valid:
+            self.compute_effective()
+        first = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        self.ctx.expand_count(N, _ptr(self.timer), _ptr(self.eff), _ptr(sel), _ptr(first), self._stream())
+        total = int(first[N].item())                    # the host wait
+        m = total if max_children is None else min(total, int(max_children))
+        return self.expand_rows(first, m, rng, sel, trust)
+
+    def expand_rows(self, first, m: int, rng, sel=None, trust: int = 1) -> "Expansion":
+        """The second half of expand(): tmg_expand into m freshly allocated
+        child rows placed by first, the (N + 1,) int64 device tensor
+        tmg_expand_count wrote for this env's timers and masks (and sel, the
+        (N, W) int64 select words, or None).  rng: the (N, 5) int64 words the
+        moves draw from; trust: tmg_expand's trust_eff."""
+        if m < 0:
+            raise ValueError("m must be >= 0")
+        if first.shape != (self.num_envs + 1,) or first.dtype != torch.int64 or first.device != self.board.device \
+                or not first.is_contiguous():
+            raise ValueError(f"first_child must be a contiguous ({self.num_envs + 1},) int64 tensor on the env's device")
+        m = int(m)
+        kw = dict(device=self.board.device)
+        board = torch.empty((m, 2, self.num_rows, self.num_cols), dtype=torch.int8, **kw)
+        crng = torch.empty((m, 5), dtype=torch.int64, **kw)
+        timer = torch.empty(m, dtype=torch.int32, **kw)
+        eff = torch.empty((m, self.mask_words), dtype=torch.int64, **kw)
+        parent = torch.empty(m, dtype=torch.int64, **kw)
+        action, reward, n_new, n_act = (torch.empty(m, dtype=torch.int32, **kw) for _ in range(4))
+        flags = torch.empty(m, dtype=torch.uint8, **kw)
+        env = None
+        if m:
+            self.ctx.expand(self.num_envs, _ptr(self.board), _ptr(rng), _ptr(self.timer), _ptr(self.eff), _ptr(sel),
+                            trust, _ptr(first), m, _ptr(board), _ptr(crng), _ptr(timer), _ptr(eff), _ptr(parent),
+                            _ptr(action), _ptr(reward), _ptr(n_new), _ptr(n_act), _ptr(flags), self._stream())
+            env = self._child_env(board, crng, timer, eff)
+        return Expansion(m, first, parent, action, reward, n_new, n_act, flags, env)
+
+    def _child_env(self, board, rng, timer, eff) -> "TileMatchVecEnv":
+        """An env over child tensors: this env's shape, colours, specials,
+        num_moves and context, autoreset mode "none", the mask cache valid, no
+        reset run, one env group."""
+        env = object.__new__(TileMatchVecEnv)
+        N = board.shape[0]
+        env.device = self.device
+        env.num_envs = N
+        env.num_rows, env.num_cols, env.num_colours, env.num_moves = \
+            self.num_rows, self.num_cols, self.num_colours, self.num_moves
+        env.colourless_specials, env.colour_specials = list(self.colourless_specials), list(self.colour_specials)
+        env.specials_mask = self.specials_mask
+        env._autoreset_mode = "none"
+        env.ctx = self.ctx                          # shared: the context holds no per-batch state
+        env._owns_ctx = False
+        env.num_actions, env.mask_words = self.num_actions, self.mask_words
+        env._dev_index = self._dev_index
+        env.board, env.rng, env.timer, env.eff = board, rng, timer, eff
+        kw = dict(device=self.device)
+        env.reward, env.n_new, env.n_act = (torch.zeros(N, dtype=torch.int32, **kw) for _ in range(3))
+        env.flags = torch.zeros(N, dtype=torch.uint8, **kw)
+        env.actions = None
+        env._peek_bufs, env._roll_bufs = {}, {}
+        env.onehot = None
+        env._oh_code = _native.DTYPE_F32
+        env._eff_valid = True
+        env.groups = 1
+        env._ranges = [(0, N)]
+        env._streams = []
+        env._plans = {pol: _native.Plan(env.ctx, N, _ptr(env.board), _ptr(env.rng), _ptr(env.timer), _ptr(env.reward),
+                                        _ptr(env.n_new), _ptr(env.n_act), _ptr(env.flags), _ptr(env.eff), [0, N], [0])
+                      for pol in (False, True)}
+        env._policy = (12345, 0)
+        env._vout = {}
+        env._held = []
+        env._configure()
+        return env
+
     def capture_steps(self, actions=None, ts=None, policy: bool = False, key: int = 12345, first_env: int = 0):
         """Capture len(ts) batched steps into a HIP graph (tmg_plan_capture):
         run_graph() then enqueues all of them with one host call, the env
@@ -627,4 +755,5 @@ class TileMatchVecEnv:
         self.join()
         for plan in self._plans.values():
             plan.close()
-        self.ctx.close()
+        if getattr(self, "_owns_ctx", True):           # an Expansion's env shares its parent's context
+            self.ctx.close()

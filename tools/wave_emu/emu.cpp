@@ -4,6 +4,7 @@
 #include "hip/hip_runtime.h"
 #include "tmg_board.hip"
 #include "tmg_aux.hip"
+#include "tmg_expand.hip"
 #include "tmg_dispatch.h"
 
 #include <setjmp.h>
@@ -445,6 +446,50 @@ int emu_rollout(int R, int C, int k, int smask, int moves, int64_t n, const int8
     if (total || best_action || best_total)
         run_blocks(n, 0, [&] { tmg::rollout_reduce_kernel(n, P.A, samples, ret, total, best_action, best_total); });
     return 0;
+}
+
+// tmg_expand_count without the context and the stream: the three launches of
+// expand_count_kernel (csrc/tmg_expand.hip), one wave per tile of envs
+int emu_expand_count(int R, int C, int moves, int64_t n, const int32_t *timer, const uint64_t *eff,
+                     const uint64_t *select, int64_t *first_child) {
+    if (n < 0 || !first_child || (n > 0 && (!timer || !eff))) return -2;
+    const int A = 2 * R * C - R - C;
+    const tmg::ExpandCountArgs a{n, (A + 63) / 64, A, moves, timer, eff, select, first_child};
+    const int64_t tiles = (n + tmg::kExpandTile - 1) / tmg::kExpandTile;
+    if (tiles) run_grid(tiles, 0, [&] { tmg::expand_count_kernel<0>(a); });
+    run_grid(1, 0, [&] { tmg::expand_count_kernel<1>(a); });
+    if (tiles) run_grid(tiles, 0, [&] { tmg::expand_count_kernel<2>(a); });
+    return 0;
+}
+
+// tmg_expand without the stream: the gather kernel, then emu_step on the m
+// child rows.  pack: 1 / 0 the gather's two store variants, -1 the library's
+// (TMG_EXPAND_PACK).  The refusals are tmg_expand's (-1 / -2).
+int emu_expand(int R, int C, int k, int smask, int moves, int64_t n, const int8_t *board, const uint64_t *rng,
+               const int32_t *timer, const uint64_t *eff, const uint64_t *select, int trust_eff,
+               const int64_t *first_child, int64_t m, int8_t *child_board, uint64_t *child_rng, int32_t *child_timer,
+               uint64_t *child_eff, int64_t *child_parent, int32_t *child_action, int32_t *child_reward,
+               int32_t *child_n_new, int32_t *child_n_act, uint8_t *child_flags, int pack) {
+    if (n < 0 || m < 0) return -2;
+    if (n == 0 || m == 0) return 0;
+    if (!board || !rng || !timer || !eff || !first_child || !child_board || !child_rng || !child_timer || !child_eff ||
+        !child_action || !child_reward || !child_n_new || !child_n_act || !child_flags)
+        return -1;
+    if (reinterpret_cast<uintptr_t>(child_board) & 7) return -2;
+    const tmg::Params P = tmg::make_params(R, C, k, smask, moves, nullptr);
+    const tmg::ExpandArgs a{n, m, P.N, P.W, P.A, P.num_moves, board, rng, timer, eff, select, first_child,
+                            child_board, child_rng, child_timer, child_eff, child_parent, child_action};
+    const bool pk = pack < 0 ? tmg::kExpandPack : pack != 0;
+    if (tmg::shape_maxn(P) == 128) {
+        if (pk) run_blocks(n, 0, [&] { tmg::expand_gather_kernel<1, true>(a); });
+        else run_blocks(n, 0, [&] { tmg::expand_gather_kernel<1, false>(a); });
+    } else {
+        if (pk) run_blocks(n, 0, [&] { tmg::expand_gather_kernel<4, true>(a); });
+        else run_blocks(n, 0, [&] { tmg::expand_gather_kernel<4, false>(a); });
+    }
+    return emu_step(R, C, k, smask, moves, m, child_board, child_rng, child_timer, child_action, child_reward,
+                    child_n_new, child_n_act, child_flags, child_eff, trust_eff, 0, 0, 0, 0, 0, nullptr, nullptr,
+                    nullptr, nullptr, nullptr);
 }
 
 // tmg_seed without the context and the stream: the same arguments and

@@ -33,6 +33,8 @@ def load(asan=False):
     L.emu_peek_route.argtypes = [I, I, I, I, I, P]
     L.emu_rollout.argtypes = [I, I, I, I, I, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32,
                               P, P, P, P, P, P]
+    L.emu_expand_count.argtypes = [I, I, I, I64, P, P, P, P]
+    L.emu_expand.argtypes = [I, I, I, I, I, I64, P, P, P, P, P, I, P, I64] + [P] * 10 + [I]
     U64 = ctypes.c_uint64
     L.emu_seed.argtypes = [I64, I, P, I, U64, U64, U64, U64, I64, P]
     return L
@@ -111,6 +113,64 @@ def rollout(L, R, C, k, smask, num_moves, board, rng, timer, eff, trust_eff, dep
                        *(out[f].ctypes.data for f in ("ret", "plies", "flags", "total", "best_action", "best_total")))
     if rc:
         raise ValueError(f"emu_rollout refused the call ({rc})")
+    return out
+
+
+def _opt(a, dtype):
+    return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+
+
+def _addr(a):
+    return None if a is None else a.ctypes.data
+
+
+def expand_count(L, R, C, num_moves, timer, eff, select=None):
+    """tmg_expand_count on the emulated kernels: the (n + 1,) int64 first_child
+    array of n envs.  eff / select: (n, W) uint64 mask words (select None: every
+    effective action); timer: (n,) int32.  The inputs are only read."""
+    timer = np.ascontiguousarray(timer, dtype=np.int32)
+    n = timer.shape[0]
+    eff = np.ascontiguousarray(eff, dtype=np.uint64)
+    select = _opt(select, np.uint64)
+    out = np.full(n + 1, -7, np.int64)
+    rc = L.emu_expand_count(R, C, int(num_moves), n, _addr(timer), _addr(eff), _addr(select), out.ctypes.data)
+    if rc:
+        raise ValueError(f"emu_expand_count refused the call ({rc})")
+    return out
+
+
+EXPAND_FIELDS = ("board", "rng", "timer", "eff", "parent", "action", "reward", "n_new", "n_act", "flags")
+
+
+def expand(L, R, C, k, smask, num_moves, board, rng, timer, eff, select=None, trust_eff=1, m=None, pack=-1):
+    """tmg_expand_count + tmg_expand on the emulated kernels, the moves by
+    emu_step on the child rows: dict of first_child (n + 1,) int64 and, per
+    child row, EXPAND_FIELDS (board (m, 2, R, C) int8, rng (m, 5) / eff (m, W)
+    uint64, timer / action / reward / n_new / n_act int32, parent int64, flags
+    uint8).  m None: first_child[n] rows; rows nothing writes keep a sentinel
+    fill (board -7, rng / eff 0xA5..., the rest -7 / 0x55).  pack: the gather's
+    store variant (-1: the library's).  The inputs are only read."""
+    n = board.shape[0]
+    A = 2 * R * C - R - C
+    W = (A + 63) // 64
+    board = np.ascontiguousarray(board, dtype=np.int8)
+    rng = np.ascontiguousarray(rng, dtype=np.uint64)
+    timer = np.ascontiguousarray(timer, dtype=np.int32)
+    eff = np.ascontiguousarray(eff, dtype=np.uint64)
+    select = _opt(select, np.uint64)
+    first = expand_count(L, R, C, num_moves, timer, eff, select)
+    m = int(first[n]) if m is None else int(m)
+    out = {"board": np.full((m, 2, R, C), -7, np.int8), "rng": np.full((m, 5), 0xA5A5A5A5A5A5A5A5, np.uint64),
+           "timer": np.full(m, -7, np.int32), "eff": np.full((m, W), 0xA5A5A5A5A5A5A5A5, np.uint64),
+           "parent": np.full(m, -7, np.int64), "action": np.full(m, -7, np.int32)}
+    out.update({f: np.full(m, -7, np.int32) for f in ("reward", "n_new", "n_act")})
+    out["flags"] = np.full(m, 0x55, np.uint8)
+    rc = L.emu_expand(R, C, k, smask, int(num_moves), n, _addr(board), _addr(rng), _addr(timer), _addr(eff),
+                      _addr(select), int(trust_eff), first.ctypes.data, m, *(out[f].ctypes.data for f in EXPAND_FIELDS),
+                      int(pack))
+    if rc:
+        raise ValueError(f"emu_expand refused the call ({rc})")
+    out["first_child"] = first
     return out
 
 

@@ -7,6 +7,7 @@ are stepped by OracleBatch.step(actions, autoreset=False).  Nothing here has a
 tolerance: every array is compared with np.array_equal."""
 import numpy as np
 
+import edge_cases
 from oracle import oracle as orc
 
 # (R, C, k, smask): 3x5 (N = 15) and 7x9 (N = 63) have child rows that start on
@@ -14,6 +15,12 @@ from oracle import oracle as orc
 EMULATED_SHAPES = [(3, 5, 2, 0), (4, 4, 2, 0), (7, 9, 10, 15), (10, 10, 4, 0), (10, 10, 4, 14), (8, 8, 3, 15)]
 # on the device also C = 64 (no bitboards) and the 512-cell family (W = 12)
 DEVICE_SHAPES = EMULATED_SHAPES + [(2, 64, 4, 0), (20, 20, 6, 15), (20, 20, 6, 0)]
+# the limits of the accepted domain (tests/edge_cases.py): 63 actions all horizontal, all
+# vertical, 64 rows of 8 (W = 15), W = 16.  On the device all four; on the emulator (8.7 s at
+# most, measured) all but 1x64, one of whose envs has a single child, which that test excludes
+LIMIT_SHAPES = list(edge_cases.LOOKAHEAD_DEVICE)
+DEVICE_SHAPES = DEVICE_SHAPES + LIMIT_SHAPES
+EMULATED_LIMIT_SHAPES = [s for s in LIMIT_SHAPES if s != (1, 64, 5, 15)]
 
 STATE = ("board", "rng", "timer", "eff")
 OUTPUTS = ("reward", "n_new", "n_act", "flags")

@@ -1,5 +1,6 @@
 """Loaders for the golden fixtures in tests/golden/ (recorded from the reference
-by tests/golden/make_goldens.py)."""
+by tests/golden/make_goldens.py) and, with sub="edge", in tests/golden/edge/
+(tests/golden/make_edge_goldens.py)."""
 import os
 
 import numpy as np
@@ -9,11 +10,12 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SHAPE_KEYS = ("R", "C", "k", "smask")
 
 
-def load_records(name, prefix="fn"):
-    """<prefix>_<name>.npz -> list of dict records (see make_goldens.pack_records).
+def load_records(name, prefix="fn", sub=""):
+    """[<sub>/]<prefix>_<name>.npz -> list of dict records (see make_goldens.pack_records).
     prefix "fn": random boards (make_goldens.py); "ref": the reference's own
-    hand-built test boards (make_ref_cases.py)."""
-    z = np.load(os.path.join(GOLDEN, f"{prefix}_{name}.npz"), allow_pickle=False)
+    hand-built test boards (make_ref_cases.py); "fn_a" / "fn_b" with sub="edge":
+    random boards of the shapes of tests/edge_cases.py."""
+    z = np.load(os.path.join(GOLDEN, sub, f"{prefix}_{name}.npz"), allow_pickle=False)
     n = int(z["n"])
     keys = [k for k in z.files if k not in ("n",) and not k.endswith("_off")]
     recs = []
@@ -35,8 +37,8 @@ def load_records(name, prefix="fn"):
     return recs
 
 
-def load_traj(name):
-    z = np.load(os.path.join(GOLDEN, f"traj_{name}.npz"), allow_pickle=False)
+def load_traj(name, sub=""):
+    z = np.load(os.path.join(GOLDEN, sub, f"traj_{name}.npz"), allow_pickle=False)
     d = {k: z[k] for k in z.files}
     R, C, k, smask, moves = (int(x) for x in d["shape"])
     d.update(R=R, C=C, k=k, smask=smask, num_moves=moves)
@@ -46,8 +48,8 @@ def load_traj(name):
     return d
 
 
-def traj_names():
-    return sorted(f[5:-4] for f in os.listdir(GOLDEN) if f.startswith("traj_") and f.endswith(".npz"))
+def traj_names(sub=""):
+    return sorted(f[5:-4] for f in os.listdir(os.path.join(GOLDEN, sub)) if f.startswith("traj_") and f.endswith(".npz"))
 
 
 def eff_words_to_bool(words, A):

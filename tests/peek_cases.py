@@ -7,6 +7,7 @@ the RNG words and reports zeros for an ineffective action."""
 import numpy as np
 
 import dispatch_cases
+import edge_cases
 from oracle import oracle as orc
 
 # (R, C, k, smask)
@@ -14,6 +15,10 @@ EXTRA = [(10, 10, 4, 0), (10, 10, 4, 14), (8, 8, 3, 15), (20, 20, 6, 15), (20, 2
 # lean, 1 colour plane, even C: peek<128,0,1,0>, which no shape above reaches
 ONE_PLANE_EVEN = (4, 4, 2, 0)
 SHAPES = list(dispatch_cases.CASES) + [dispatch_cases.ROW_PLANE_CONTROL] + EXTRA + [ONE_PLANE_EVEN]
+# the limits of the accepted domain (tests/edge_cases.py): 63 actions all horizontal, all
+# vertical, 64 rows of 8, 16 mask words.  Only the *_vs_oracle tests take them, on the device
+# and, each running in under 3 s there, on the emulator (measured: peek 1.4 s, rollout 2.9 s)
+LIMIT_SHAPES = list(edge_cases.LOOKAHEAD_DEVICE)
 # the adversarial boards of the untrusted / spill tests (tests/adversarial.py)
 ADVERSARIAL_SHAPES = [(20, 20, 6, 15), (10, 10, 4, 14), (8, 8, 3, 15)]
 

@@ -54,7 +54,7 @@ def test_count_scan(emu_lib, shape, n):
     assert all(np.array_equal(x, y) for x, y in zip(before, (eff, sel, timer)))
 
 
-@pytest.mark.parametrize("shape", expand_cases.EMULATED_SHAPES, ids=expand_cases.case_id)
+@pytest.mark.parametrize("shape", expand_cases.EMULATED_SHAPES + expand_cases.EMULATED_LIMIT_SHAPES, ids=expand_cases.case_id)
 def test_expand_vs_oracle(emu_lib, shape):
     """After a reset and after 7 uniform-random steps, with the envs' own RNG
     words and with words of other seeds; every env has at least two children."""

@@ -1,5 +1,9 @@
 """GPU parity: the HIP path (through the C ABI) against the reference's golden
-vectors and against the CPU oracle.  Bit-exact everywhere (integer work)."""
+vectors and against the CPU oracle.  Bit-exact everywhere (integer work).
+
+The checks of the function-level records are functions of the records, so
+that tests/test_gpu_edge.py runs the same ones on the fixtures of the shape
+limits (tests/golden/edge/)."""
 import numpy as np
 import pytest
 import torch
@@ -68,10 +72,9 @@ def _by_shape(recs):
     return g
 
 
-def test_move_golden_gpu():
-    """Board.move (board.py:330-395) from arbitrary boards with specials, RNG-exact."""
+def check_move_gpu(records, at_least):
     total = 0
-    for (R, C, k, sm), recs in _by_shape(load_records("move")).items():
+    for (R, C, k, sm), recs in _by_shape(records).items():
         recs = [r for r in recs if not r["err"]]
         if not recs:
             continue
@@ -99,12 +102,16 @@ def test_move_golden_gpu():
             assert bool(f[i] & 2) == bool(res[1]) and bool(f[i] & 4) == bool(res[4])
             assert not (f[i] & 0xC0)
         total += n
-    assert total > 500
+    assert total > at_least
 
 
-def test_effective_golden_gpu():
-    """is_move_effective (board.py:735-787) over every action, arbitrary boards."""
-    for (R, C, k, sm), recs in _by_shape(load_records("effective")).items():
+def test_move_golden_gpu():
+    """Board.move (board.py:330-395) from arbitrary boards with specials, RNG-exact."""
+    check_move_gpu(load_records("move"), 500)
+
+
+def check_effective_gpu(records):
+    for (R, C, k, sm), recs in _by_shape(records).items():
         ctx = _ctx(R, C, k, sm)
         n = len(recs)
         board = torch.from_numpy(np.stack([r["board"] for r in recs]).astype(np.int8)).to(DEV)
@@ -115,6 +122,11 @@ def test_effective_golden_gpu():
         got = eff_words_to_bool(eff.cpu().numpy().view(np.uint64), ctx.num_actions)
         for i, r in enumerate(recs):
             assert np.array_equal(got[i], r["eff"].astype(bool)), f"shape {(R, C, k, sm)} rec {i}"
+
+
+def test_effective_golden_gpu():
+    """is_move_effective (board.py:735-787) over every action, arbitrary boards."""
+    check_effective_gpu(load_records("effective"))
 
 
 @pytest.mark.parametrize("R,C,k,sm", [(10, 10, 6, 0), (9, 9, 5, 15), (20, 20, 6, 15), (9, 15, 15, 0)])
@@ -140,10 +152,9 @@ def test_generate_lemire_rejection_gpu(R, C, k, sm):
     assert np.array_equal(eff.cpu().numpy().view(np.uint64), o.eff)
 
 
-def test_generate_golden_gpu():
-    """generate_board (board.py:95-131) seeded like tile_match_env.py:49."""
+def check_generate_gpu(records):
     from tile_match_gym_amd.seeding import rng_words_from_seed
-    for (R, C, k, sm), recs in _by_shape(load_records("generate")).items():
+    for (R, C, k, sm), recs in _by_shape(records).items():
         ctx = _ctx(R, C, k, sm)
         n = len(recs)
         board = torch.zeros((n, 2, R, C), dtype=torch.int8, device=DEV)
@@ -155,6 +166,11 @@ def test_generate_golden_gpu():
         b = board.cpu().numpy()
         for i, r in enumerate(recs):
             assert np.array_equal(b[i], r["out"]), f"shape {(R, C, k, sm)} rec {i}"
+
+
+def test_generate_golden_gpu():
+    """generate_board (board.py:95-131) seeded like tile_match_env.py:49."""
+    check_generate_gpu(load_records("generate"))
 
 
 RANDOM_ACTION_CFGS = [

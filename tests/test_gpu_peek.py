@@ -59,7 +59,7 @@ def _peek(env, rng=None):
     return {f: v.cpu().numpy() for f, v in out.items()}
 
 
-@pytest.mark.parametrize("shape", peek_cases.SHAPES, ids=peek_cases.case_id)
+@pytest.mark.parametrize("shape", peek_cases.SHAPES + peek_cases.LIMIT_SHAPES, ids=peek_cases.case_id)
 def test_peek_vs_oracle_gpu(shape):
     """After 7 uniform-random steps (boards that hold specials) and after a
     reset, with the envs' own RNG words and with words of other seeds."""

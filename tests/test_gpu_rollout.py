@@ -68,7 +68,7 @@ def _want(o, rng, timer, depth, samples):
     return oracle_rollout(o.board, rng, timer, o.num_moves, o.k, o.smask, depth, samples, rc.KEY, rc.FIRST_ENV, rc.T)
 
 
-@pytest.mark.parametrize("shape", peek_cases.SHAPES, ids=peek_cases.case_id)
+@pytest.mark.parametrize("shape", peek_cases.SHAPES + peek_cases.LIMIT_SHAPES, ids=peek_cases.case_id)
 def test_rollout_vs_oracle_gpu(shape):
     """After 7 uniform-random steps (boards that hold specials) and after a
     reset; env 0 two moves from the end of its episode and, after the reset,

@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import edge_cases as ec
 from dispatch_cases import CASES as DISPATCH_CASES
 from golden_io import load_traj, traj_names, replay_trajectory
 
@@ -52,6 +53,21 @@ def test_trajectory_golden_emulated(emu_lib, name, autoreset, monkeypatch):
     emu, L = emu_lib
     monkeypatch.setenv("EMU_EPW", "1")      # one env per workgroup, as libtmg launches
     d = load_traj(name)
+    assert replay_trajectory(d, _EmuBackend(emu, L, d), autoreset) > 0
+
+
+EDGE_TRAJ = [(n, s) for n, s in ec.traj_cases() if n not in ec.EMU_SLOW]
+
+
+@pytest.mark.parametrize("name,shape", EDGE_TRAJ, ids=[n for n, _ in EDGE_TRAJ])
+@pytest.mark.parametrize("autoreset", [False, True])
+def test_edge_trajectory_golden_emulated(emu_lib, name, shape, autoreset, monkeypatch):
+    """The reference's trajectories at the shape limits (tests/edge_cases.py);
+    edge_cases.EMU_SLOW names the ones left to the oracle and the device."""
+    emu, L = emu_lib
+    assert not any(s[0] * s[1] <= 128 for n, s in ec.traj_cases() if n in ec.EMU_SLOW)
+    monkeypatch.setenv("EMU_EPW", "1")
+    d = load_traj(name, ec.SUB)
     assert replay_trajectory(d, _EmuBackend(emu, L, d), autoreset) > 0
 
 
@@ -143,13 +159,9 @@ def test_generate_lemire_rejection_emulated(emu_lib, cfg):
     assert not np.array_equal(o.rng, w), "the reset consumed the stream"
 
 
-def test_move_golden_emulated(emu_lib):
-    """Board.move (board.py:330-395) from the recorded arbitrary boards (specials, coloured cookies,
-    empties), through the emulated general kernel — the CPU twin of test_move_golden_gpu."""
-    from golden_io import load_records
-    emu, L = emu_lib
+def _check_move_emulated(emu, L, records, at_least):
     groups = {}
-    for r in load_records("move"):
+    for r in records:
         if not r["err"]:
             groups.setdefault((r["R"], r["C"], r["k"], r["smask"]), []).append(r)
     total = 0
@@ -165,7 +177,25 @@ def test_move_golden_emulated(emu_lib):
             assert np.array_equal(b.rng[i], r["rng_out"]), f"rng {(R, C, k, sm)} rec {i}"
             assert (b.reward[i], b.n_new[i], b.n_act[i]) == (res[0], res[2], res[3]), f"counters {(R, C, k, sm)} rec {i}"
         total += n
-    assert total > 500
+    assert total > at_least
+
+
+def test_move_golden_emulated(emu_lib):
+    """Board.move (board.py:330-395) from the recorded arbitrary boards (specials, coloured cookies,
+    empties), through the emulated general kernel — the CPU twin of test_move_golden_gpu."""
+    from golden_io import load_records
+    emu, L = emu_lib
+    _check_move_emulated(emu, L, load_records("move"), 500)
+
+
+@pytest.mark.parametrize("group", list(ec.GROUPS))
+def test_edge_move_golden_emulated(emu_lib, group):
+    """The same at the shape limits (tests/edge_cases.py): every record, the CPU twin of test_edge_move_gpu."""
+    from golden_io import load_records
+    emu, L = emu_lib
+    recs = load_records("move", f"fn_{group}", ec.SUB)
+    assert len(recs) == ec.FN_PER_SHAPE * len(ec.fn_shapes(group))
+    _check_move_emulated(emu, L, recs, len(recs) - 1)
 
 
 @pytest.mark.parametrize("name", ["c5_20x20k6", "gen_512_11x12k10", "gen_sb_6x6k7", "lean_512_9x15k15",

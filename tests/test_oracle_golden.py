@@ -1,5 +1,8 @@
 """Pins the CPU oracle (oracle/tmg_oracle.c) to vectors recorded from the
-reference itself (tests/golden/make_goldens.py).  No GPU needed."""
+reference itself (tests/golden/make_goldens.py).  No GPU needed.
+
+Each check is a function of the records, so that tests/test_edge_golden.py
+runs the same checks on the fixtures of the shape limits (tests/golden/edge/)."""
 import numpy as np
 import pytest
 
@@ -7,9 +10,8 @@ from golden_io import load_records, load_traj, traj_names, replay_trajectory
 from oracle import oracle as orc
 
 
-def test_get_colour_lines_golden():
-    """board.py:149-215 — exact list (order matters downstream)."""
-    for r in load_records("lines"):
+def check_get_colour_lines(recs):
+    for r in recs:
         got = orc.get_colour_lines(r["board"], r["k"], r["smask"])
         C = r["C"]
         exp, o = [], 0
@@ -19,10 +21,14 @@ def test_get_colour_lines_golden():
         assert got == exp
 
 
-def test_process_colour_lines_golden():
-    """board.py:269-327 via detect_colour_matches :133-147."""
+def test_get_colour_lines_golden():
+    """board.py:149-215 — exact list (order matters downstream)."""
+    check_get_colour_lines(load_records("lines"))
+
+
+def check_process_colour_lines(recs, at_least):
     n = 0
-    for r in load_records("lines"):
+    for r in recs:
         if r["perr"]:
             continue
         coords, names, cols = orc.process_lines(r["board"], r["k"], r["smask"])
@@ -34,27 +40,52 @@ def test_process_colour_lines_golden():
         assert np.array_equal(names, r["pnames"])
         assert np.array_equal(cols, r["pcols"])
         n += len(exp)
-    assert n > 100
+    assert n > at_least
 
 
-def test_is_move_effective_golden():
-    """board.py:735-787 and possible_move :558-569."""
-    for r in load_records("effective"):
+def test_process_colour_lines_golden():
+    """board.py:269-327 via detect_colour_matches :133-147."""
+    check_process_colour_lines(load_records("lines"), 100)
+
+
+def check_is_move_effective(recs):
+    for r in recs:
         m, any_ = orc.effective_mask(r["board"])
         assert np.array_equal(m, r["eff"].astype(bool))
         assert any_ == bool(r["possible"])
 
 
+def test_is_move_effective_golden():
+    """board.py:735-787 and possible_move :558-569."""
+    check_is_move_effective(load_records("effective"))
+
+
+def check_gravity(recs):
+    for r in recs:
+        assert np.array_equal(orc.gravity(r["board"]), r["out"])
+
+
 def test_gravity_golden():
     """board.py:217-229."""
-    for r in load_records("gravity"):
-        assert np.array_equal(orc.gravity(r["board"]), r["out"])
+    check_gravity(load_records("gravity"))
+
+
+def check_activate_special(recs):
+    for r in recs:
+        out, na, err = orc.activate(r["board"], r["cell"], r["combo"], r["k"], r["smask"])
+        assert err == 0
+        assert np.array_equal(out, r["out"])
+        assert na == r["n_act"]
 
 
 def test_activate_special_golden():
     """board.py:473-556 (recursive DFS, cookie argmax)."""
-    for r in load_records("activate"):
-        out, na, err = orc.activate(r["board"], r["cell"], r["combo"], r["k"], r["smask"])
+    check_activate_special(load_records("activate"))
+
+
+def check_combination_match(recs):
+    for r in recs:
+        out, na, err = orc.combination(r["board"], r["action"], r["k"], r["smask"])
         assert err == 0
         assert np.array_equal(out, r["out"])
         assert na == r["n_act"]
@@ -62,17 +93,12 @@ def test_activate_special_golden():
 
 def test_combination_match_golden():
     """board.py:600-719."""
-    for r in load_records("combo"):
-        out, na, err = orc.combination(r["board"], r["action"], r["k"], r["smask"])
-        assert err == 0
-        assert np.array_equal(out, r["out"])
-        assert na == r["n_act"]
+    check_combination_match(load_records("combo"))
 
 
-def test_detect_resolve_golden():
-    """board.py:397-471 + 572-597 (one cascade iteration, no gravity/refill)."""
+def check_detect_resolve(recs, at_least):
     n = 0
-    for r in load_records("resolve"):
+    for r in recs:
         if r["err"]:
             continue
         out, na, nn, err = orc.detect_resolve(r["board"], r["k"], r["smask"])
@@ -80,13 +106,17 @@ def test_detect_resolve_golden():
         assert np.array_equal(out, r["out"])
         assert (na, nn) == (r["n_act"], r["n_new"])
         n += 1
-    assert n > 100
+    assert n > at_least
 
 
-def test_move_golden():
-    """board.py:330-395 incl. refill RNG draws and the ensure-playable loop."""
+def test_detect_resolve_golden():
+    """board.py:397-471 + 572-597 (one cascade iteration, no gravity/refill)."""
+    check_detect_resolve(load_records("resolve"), 100)
+
+
+def check_move(recs, at_least):
     n = 0
-    for r in load_records("move"):
+    for r in recs:
         if r["err"]:
             continue
         out, rng, res, err = orc.move(r["board"], r["rng_in"], r["action"], r["k"], r["smask"])
@@ -95,15 +125,24 @@ def test_move_golden():
         assert np.array_equal(rng, r["rng_out"])
         assert np.array_equal(res, r["res"])
         n += 1
-    assert n > 500
+    assert n > at_least
+
+
+def test_move_golden():
+    """board.py:330-395 incl. refill RNG draws and the ensure-playable loop."""
+    check_move(load_records("move"), 500)
+
+
+def check_generate_board(recs):
+    from tile_match_gym_amd.seeding import rng_words_from_seed
+    for r in recs:
+        b, _ = orc.generate(r["R"], r["C"], r["k"], r["smask"], rng_words_from_seed(int(r["seed"])))
+        assert np.array_equal(b, r["out"])
 
 
 def test_generate_board_golden():
     """board.py:95-131 seeded exactly like tile_match_env.py:49."""
-    for r in load_records("generate"):
-        from tile_match_gym_amd.seeding import rng_words_from_seed
-        b, _ = orc.generate(r["R"], r["C"], r["k"], r["smask"], rng_words_from_seed(int(r["seed"])))
-        assert np.array_equal(b, r["out"])
+    check_generate_board(load_records("generate"))
 
 
 def test_rng_matches_numpy():

@@ -27,7 +27,7 @@ def emu_lib():
     return emu, emu.load()
 
 
-@pytest.mark.parametrize("shape", peek_cases.SHAPES, ids=peek_cases.case_id)
+@pytest.mark.parametrize("shape", peek_cases.SHAPES + peek_cases.LIMIT_SHAPES, ids=peek_cases.case_id)
 def test_peek_vs_oracle(emu_lib, shape):
     """After a reset and after 7 uniform-random steps (boards that hold
     specials), with the envs' own RNG words and with words of other seeds."""

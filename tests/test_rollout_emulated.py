@@ -42,7 +42,7 @@ def _rollout(emu, L, shape, board, rng, timer, eff, trust_eff, depth, samples, k
     return emu.rollout(L, R, C, k, sm, MOVES, board, rng, timer, eff, trust_eff, depth, samples, key, first_env, t)
 
 
-@pytest.mark.parametrize("shape", peek_cases.SHAPES, ids=peek_cases.case_id)
+@pytest.mark.parametrize("shape", peek_cases.SHAPES + peek_cases.LIMIT_SHAPES, ids=peek_cases.case_id)
 def test_rollout_vs_oracle(emu_lib, shape):
     """After 7 uniform-random steps (boards that hold specials) and after a
     reset; env 0 two moves from the end of its episode and, after the reset,

@@ -221,3 +221,93 @@ def test_every_instantiation_runs_with_fused_outputs(emu_lib):
     assert steps == ALL_STEPS, f"never launched: {sorted(ALL_STEPS - steps)}, not in the ladders: {sorted(steps - ALL_STEPS)}"
     assert deferred == ALL_RESETS - never, (f"never deferred: {sorted(ALL_RESETS - never - deferred)}, "
                                             f"not expected: {sorted(deferred - (ALL_RESETS - never))}")
+
+
+# The route classes tests/extent_cases.py EXTENT_SHAPES are there for, written out by
+# hand: name -> what one of the shapes has to reach.  step / untrusted / reset / peek:
+# the instantiation of a trusted step, of a step with trust_eff = 0, of a reset, of a
+# trusted peek; route: fields of the trusted same-step route; A, bytes2N: the action
+# count and the bytes of a board; lane: the lane kernel takes the in-kernel policy at
+# every batch size of the shape and at LANE_SMALL + 1, and given actions at LANE_MIN + 1.
+EXTENT_CLASSES = {
+    "lean bitboard, odd C, byte stores": dict(step=(128, 0, 1, 1, NOFIX), reset=(128, 1, 1, NOFIX), route=LEAN_INLINE,
+                                              peek=(128, 0, 1, 1), A=22, bytes2N=30),
+    "general bitboard, odd C": dict(step=(128, 1, 3, 1, NOFIX), reset=(128, 3, 1, NOFIX), route=GEN128,
+                                    peek=(128, 1, 3, 1), bytes2N=126),
+    "c2 and the lane kernel, k = 4": dict(step=(128, 0, 2, 0, FIX_C2), reset=(128, 2, 0, FIX_RESET10), route=LEAN_INLINE,
+                                          lane=True),
+    "the lane kernel, k = 5": dict(step=(128, 0, 3, 0, NOFIX), reset=(128, 3, 0, NOFIX), route=LEAN_INLINE, lane=True),
+    "c3, deferred reset at 8 envs per wave, spill": dict(step=(128, 1, 2, 0, FIX_C3), reset=(128, 2, 0, FIX_RESET10),
+                                                         route=GEN128),
+    "A = 64, lean": dict(step=(128, 0, 2, 0, NOFIX), route=LEAN_INLINE, A=64),
+    "A = 64, general": dict(step=(128, 1, 2, 0, NOFIX), route=GEN128, A=64),
+    "no bitboards": dict(step=(128, 0, 0, 0, NOFIX), untrusted=(128, 1, 0, 0, NOFIX), reset=(128, 0, 0, NOFIX),
+                         peek=(128, 0, 0, 0)),
+    "c5, deferred reset at 2 envs per wave, spill": dict(step=(512, 1, 0, 0, FIX_C5), reset=(512, 3, 0, FIX_RESET20),
+                                                         route=GEN512, peek=(512, 1, 0, 0)),
+    "lean 512-cell": dict(step=(512, 0, 0, 0, NOFIX), reset=(512, 4, 0, NOFIX), route=LEAN512, peek=(512, 0, 0, 0)),
+}
+
+
+def _reaches(emu, L, shape, sizes, want):
+    """Whether the shape reaches the class `want` of EXTENT_CLASSES."""
+    R, C = shape[:2]
+    st, rt = emu.route(L, *shape)
+    ut, _ = emu.route(L, *shape, trust_eff=0)
+    inst = lambda r: tuple(r[f] for f in ("MAXN", "GEN", "NB", "CODD", "FIX"))      # noqa: E731
+    ok = inst(st) == want["step"]
+    if "untrusted" in want:
+        ok &= inst(ut) == want["untrusted"] and ut["spill"] == 1
+    if "reset" in want:
+        ok &= tuple(rt[f] for f in ("MAXN", "NB", "CODD", "FIX")) == want["reset"]
+    if "route" in want:
+        ok &= {f: st[f] for f in want["route"]} == want["route"]
+    if "peek" in want:
+        ok &= tuple(emu.peek_route(L, *shape)[f] for f in emu.PEEK_ROUTE) == want["peek"]
+    if "A" in want:
+        ok &= 2 * R * C - R - C == want["A"]
+    if "bytes2N" in want:
+        ok &= 2 * R * C == want["bytes2N"]
+    lane = all(emu.route(L, *shape, n=n, have_lane=True, policy=True, mode=mode)[0]["lane"] == 1
+               for n in sizes + (32769,) for mode in (1, 2))
+    given = emu.route(L, *shape, n=LANE_MIN + 1, have_lane=True)[0]
+    return ok and lane == (given["lane"] == 1) == want.get("lane", False)
+
+
+def test_extent_shapes_reach_every_route_class(emu_lib):
+    """tests/extent_cases.py EXTENT_SHAPES (test_gpu_extent.py on the device,
+    tools/wave_emu/extent_asan.cpp on the host) has one row per class of
+    EXTENT_CLASSES, and each class is reached by exactly one row: deleting a row
+    leaves a class without a shape.  The batch sizes are the ragged ones (1, 9,
+    65; 1, 3, 9 on 512-cell boards; 1, 9 where the oracle generates slowly), the
+    masked resets run at 8 and at 2 envs per wave, 2 also behind the lane kernel,
+    and the lane cases of the device test are the lane kernel's."""
+    import extent_cases as ec
+    import fused_cases as fc
+    emu, L = emu_lib
+    assert len(set(ec.EXTENT_SHAPES)) == len(ec.EXTENT_SHAPES)
+    for name, want in EXTENT_CLASSES.items():
+        hits = [s for s in ec.EXTENT_SHAPES if _reaches(emu, L, s, ec.batch_sizes(s), want)]
+        assert len(hits) == 1, f"{name}: reached by {hits}"
+    for s in ec.EXTENT_SHAPES:
+        want = (1, 9) if s in fc.SLOW else (1, 9, 65) if s[0] * s[1] <= 128 else (1, 3, 9)
+        assert ec.batch_sizes(s) == want, s
+    assert {(s, n) for s in ec.EXTENT_SHAPES for n in ec.batch_sizes(s)} == set(ec.CASES)
+    assert set(ec.GROUPS) == set(ec.RUN) and len(ec.GROUPS) == 7
+    # envs per wave of the deferred resets: 8 and 2 behind the wave kernels, 2 behind the lane kernel
+    epw = {(bool(st["lane"]), st["reset_epw"]) for s in ec.EXTENT_SHAPES for pol in (False, True)
+           for st in [emu.route(L, *s, n=9, have_lane=True, policy=pol)[0]] if st["deferred"]}
+    assert epw == {(False, 8), (False, 2), (True, 2)}, epw
+    assert {emu.route(L, *s)[1]["epw_masked"] for s in ec.EXTENT_SHAPES} == {8, 2}
+    # the lane cases: 32 envs per wave below LANE_SMALL, 64 from there on, and the given-action route past LANE_MIN
+    assert (ec.LANE_SMALL, ec.LANE_MIN) == (32768, LANE_MIN)
+    assert set(ec.LANE_CASES) == {(s, n) for s in [(10, 10, 4, 0), (10, 10, 5, 0)] for n in (1, 9, 65, 32769)}
+    for s, n in ec.LANE_CASES:
+        for mode in (1, 2):
+            st, _ = emu.route(L, *s, n=n, have_lane=True, policy=True, mode=mode)
+            assert (st["lane"], st["deferred"], st["reset_epw"]) == (1, 1, 2), (s, n, mode)
+    st, _ = emu.route(L, 10, 10, 4, 0, n=ec.LANE_MIN + 1, have_lane=True)        # test_extent_lane_given_actions
+    assert (st["lane"], st["deferred"], st["reset_epw"]) == (1, 1, 2)
+    assert set(ec.SPILL_SHAPES) == {(10, 10, 4, 14), (20, 20, 6, 15)} <= set(ec.EXTENT_SHAPES)
+    for s in ec.SPILL_SHAPES:
+        assert emu.route(L, *s, trust_eff=0)[0]["spill"] == 1

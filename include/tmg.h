@@ -186,6 +186,65 @@ TMG_API int tmg_rollout(tmg_ctx *ctx, int64_t n, const int8_t *board,
                         int32_t *best_total,      /* [n] that total, or NULL */
                         void *stream);
 
+/* Given action sequences played on copies of every env, without changing any
+ * state: what a shooting planner asks (random shooting, CEM, beam refinement,
+ * the replay of a recorded trajectory).  Row (q, i), for every sequence q in
+ * [0, seqs) and env i, is exactly what successive tmg_step(autoreset = 0) calls
+ * with actions[q][i][0], [1], ... leave and report on a one-env copy of env i
+ * whose RNG words are rng[i] (rng[q][i] when rng_per_seq != 0).
+ *   An effective action is Board.move (board.py:330-395); the RNG stream runs
+ *     on from ply to ply.  An ineffective action is a move like any other
+ *     (board.py:352-353, tile_match_env.py:100): reward 0, board and RNG words
+ *     unchanged, it counts in plies and the timer goes up by one.  trust_eff
+ *     as tmg_rollout: non-zero, eff is this library's mask and the lean
+ *     kernels run when no special is enabled; zero, eff may be NULL, the mask
+ *     is scanned and hand-edited boards work.
+ *   A negative action ends the sequence quietly (padding of ragged
+ *     sequences): a sequence that starts with one has plies = 0, zero sums and
+ *     flags, and its final state is its parent's.
+ *   An action >= A is what a bad action is to a step: TMG_FLAG_ERROR in flags,
+ *     the sequence stops before that ply with the state as the ply before left
+ *     it, and TMG_STATUS_CALLER is raised.
+ *   Horizon: H = depth when timer is NULL, else min(depth, num_moves -
+ *     timer[i]); a sequence never steps after done.  One that reaches
+ *     num_moves carries TMG_FLAG_DONE and an all-zero out_eff row
+ *     (tile_match_env.py:119-120).  H <= 0, a finished env: zeros, and a final
+ *     state that is a copy of the parent with a zero mask.
+ *   ret / n_new / n_act: the sums over the plies played of the steps' reward
+ *     / n_new / n_act; plies: how many were played; ply_reward[q][i][d]: ply
+ *     d's reward, 0 for plies not played; flags: the OR of the plies'
+ *     TMG_FLAG_COMBO | SHUFFLED | ERROR, plus DONE.  A ply that ends on a
+ *     safety cap sets TMG_FLAG_ERROR, stops that sequence (the ply counted) and
+ *     raises TMG_STATUS_INTERNAL; a lean launch that loads a non-normal tile
+ *     flags every sequence of that env and plays none, as tmg_peek does.
+ *   out_board / out_rng / out_timer / out_eff: the state after the last ply
+ *     played, out_timer = timer[i] + plies (it needs timer), out_eff the
+ *     library's own mask of out_board: the rows can be stepped, peeked or
+ *     expanded with trust_eff = 1.
+ *   best_seq[i]: the lowest q of maximal ret[q][i], best_ret[i] that value
+ *     (any seqs); both need ret.
+ *   Nothing of board, rng, timer, eff or actions is written.  A virtual env
+ *     one of whose plies outgrew the kernels' LDS lists is re-run whole on the
+ *     worst-case lists and counts in tmg_spills.
+ *   Refused: a tmg_create_scan context, n < 0, seqs < 1, depth < 1, n * seqs
+ *     above 2^26 - 8 (one wave each), a null board, rng or actions with n > 0,
+ *     trust_eff != 0 with a null eff, out_timer without timer, best_seq /
+ *     best_ret without ret, an out_board that is not 8-byte aligned (the
+ *     lane-per-board step reads boards as 8-byte words).  n == 0 is a no-op.
+ *     Asynchronous on `stream`. */
+TMG_API int tmg_playout(tmg_ctx *ctx, int64_t n, const int8_t *board,
+                        const uint64_t *rng, int rng_per_seq,   /* [n][5], or [seqs][n][5] when rng_per_seq != 0; only read */
+                        const int32_t *timer,                   /* [n] or NULL (no horizon) */
+                        const uint64_t *eff, int trust_eff,
+                        int seqs, int depth,
+                        const int32_t *actions,                 /* [seqs][n][depth] */
+                        int32_t *ret, int32_t *n_new, int32_t *n_act,   /* [seqs][n] sums over the plies, each or NULL */
+                        int32_t *plies, uint8_t *flags,         /* [seqs][n], each or NULL */
+                        int32_t *ply_reward,                    /* [seqs][n][depth] or NULL */
+                        int8_t *out_board, uint64_t *out_rng, int32_t *out_timer, uint64_t *out_eff, /* [seqs][n]..., each or NULL */
+                        int32_t *best_seq, int32_t *best_ret,   /* [n], each or NULL; need ret */
+                        void *stream);
+
 /* Successor states of every effective action: the expansion step of a tree
  * search that keeps its children (board, RNG position, timer, mask), to peek,
  * roll out, expand again or score them.  Two calls: tmg_expand_count places

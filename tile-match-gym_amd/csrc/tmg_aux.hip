@@ -145,6 +145,31 @@ __global__ __launch_bounds__(64) void rollout_reduce_kernel(int64_t n, int A, in
     }
 }
 
+// tmg_playout's best sequence per env (launched behind the playout kernels on
+// their stream): the lowest q of maximal ret[q][e], and that value.  One wave
+// per env in wg_env's order, built like rollout_reduce_kernel: lane l takes the
+// sequences l, l + 64, ... (any seqs, ascending, so `>` keeps the lowest), then
+// a wave-wide maximum of the lanes' bests and, among the lanes holding it, of
+// the negated sequence index.  best_seq / best_ret: each may be null.
+__global__ __launch_bounds__(64) void playout_reduce_kernel(int64_t n, int seqs, const int32_t *__restrict__ ret,
+                                                            int32_t *__restrict__ best_seq,
+                                                            int32_t *__restrict__ best_ret) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = wg_env();
+    if (e >= n) return;
+    int bv = (int)0x80000000, bq = 0x7fffffff;     // this lane's best (returns are >= 0)
+    for (int q = lane; q < seqs; q += 64) {
+        const int r = ret[(int64_t)q * n + e];
+        if (r > bv) { bv = r; bq = q; }
+    }
+    const int mx = wave_max(bv);
+    const int lowest = -wave_max(bv == mx ? -bq : (int)0x80000000);
+    if (lane == 0) {
+        if (best_seq) best_seq[e] = lowest;
+        if (best_ret) best_ret[e] = mx;
+    }
+}
+
 // utils.compute_num_states / is_valid_state (src/tile_match_gym/utils/utils.py:6-26):
 // over every colouring of an all-normal R x C board with colours 1..k (the
 // itertools.product order: cell 0 is the most significant digit), count the

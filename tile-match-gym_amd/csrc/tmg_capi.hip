@@ -555,6 +555,52 @@ int tmg_rollout(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rn
 // one wave per env (or child row): the padded grid's threads must stay below 2^32
 static constexpr int64_t kMaxWaveRows = (1LL << 26) - 8;
 
+int tmg_playout(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, int rng_per_seq,
+                const int32_t *timer, const uint64_t *eff, int trust_eff, int seqs, int depth, const int32_t *actions,
+                int32_t *ret, int32_t *n_new, int32_t *n_act, int32_t *plies, uint8_t *flags, int32_t *ply_reward,
+                int8_t *out_board, uint64_t *out_rng, int32_t *out_timer, uint64_t *out_eff, int32_t *best_seq,
+                int32_t *best_ret, void *stream) {
+    int rc = check_full(ctx, n);
+    if (rc) return rc;
+    if (seqs < 1) return fail(-2, "playout needs >= 1 sequence");
+    if (depth < 1) return fail(-2, "playout depth must be >= 1");
+    if (n > kMaxWaveRows / seqs) return fail(-2, "n * seqs is more than one launch holds (2^26 - 8 waves)");
+    if (out_timer && !timer) return fail(-1, "out_timer needs timer");
+    if ((best_seq || best_ret) && !ret) return fail(-1, "best_seq / best_ret need ret");
+    // the rows are stepped on: the lane-per-board step reads boards as 8-byte
+    // words (tmg_lane.h), and store_board writes them as dwords
+    if (reinterpret_cast<uintptr_t>(out_board) & 7) return fail(-2, "out_board must be 8-byte aligned");
+    if (n == 0) return 0;
+    if (!board || !rng || !actions) return fail(-1, "null state or actions buffer");
+    if (trust_eff && !eff) return fail(-1, "trust_eff != 0 needs the effective-action mask");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int64_t nv = n * seqs;
+    Params P = ctx->P;
+    // peek's route: lean kernels for a trusted mask with no special enabled,
+    // else the general ones with the spill pass behind them
+    const bool lean = tmg::lean_step(P, trust_eff);
+    if (!lean) {
+        rc = spill_for(ctx, s, nv, &P.spill, &P.spill_ws);
+        if (rc) return rc;
+    }
+    const tmg::PlayArgs a{n, seqs, depth, board, rng, rng_per_seq ? 1 : 0, timer, eff, trust_eff ? 1 : 0, actions,
+                          ret, n_new, n_act, plies, flags, ply_reward, out_board, out_rng, out_timer, out_eff};
+    const dim3 grid = tmg::env_grid(nv);
+    if (lean) tmg::launch_playout_lean(ctx->maxn, ctx->sb, grid, s, P, a);
+    else tmg::launch_playout_gen(ctx->maxn, ctx->sb, grid, s, P, a);
+    rc = hip_check(hipGetLastError(), "kernel launch");
+    if (rc) return rc;
+    if (!lean) {                                   // re-run the virtual envs that ran out of LDS list space
+        if (ctx->maxn == 128) tmg::launch_playout_spill128(s, P, a);
+        else tmg::launch_playout_spill512(s, P, a);
+        rc = hip_check(hipGetLastError(), "kernel launch");
+        if (rc) return rc;
+    }
+    if (!best_seq && !best_ret) return 0;
+    tmg::launch_playout_reduce(s, n, seqs, ret, best_seq, best_ret);
+    return hip_check(hipGetLastError(), "kernel launch");
+}
+
 int tmg_expand_count(tmg_ctx *ctx, int64_t n, const int32_t *timer, const uint64_t *eff, const uint64_t *select,
                      int64_t *first_child, void *stream) {
     int rc = check_full(ctx, n);
@@ -908,7 +954,7 @@ __attribute__((visibility("default"))) int tmg_debug_cover(tmg_ctx *ctx, uint64_
 int tmg_num_actions(const tmg_ctx *ctx) { return ctx ? ctx->P.A : -1; }
 int tmg_mask_words(const tmg_ctx *ctx) { return ctx ? ctx->P.W : -1; }
 const char *tmg_last_error(void) { return g_err.c_str(); }
-int tmg_abi_version(void) { return 8; }
+int tmg_abi_version(void) { return 9; }
 const char *tmg_build_info(void) { return "src=" TMG_SRC_SHA ";variant=" TMG_VARIANT; }
 
 }  // extern "C"

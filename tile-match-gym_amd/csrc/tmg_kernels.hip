@@ -1,5 +1,5 @@
 // tmg_kernels.hip — kernel instantiations and their host launchers
-// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..12, so the
+// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..14, so the
 // heavy template instantiations build in parallel; each TU registers only its
 // own kernels.
 #include <hip/hip_runtime.h>
@@ -27,7 +27,7 @@
 #endif
 
 #ifndef TMG_TU
-#error "compile tmg_kernels.hip with -DTMG_TU=1..12"
+#error "compile tmg_kernels.hip with -DTMG_TU=1..14"
 #endif
 
 namespace tmg {
@@ -128,7 +128,43 @@ void rollout_spill_one(hipStream_t s, const Params &P, const RollArgs &a) {
     hipLaunchKernelGGL((rollout_spill_kernel<MAXN>), dim3(kSpillWaves), dim3(64), lds, s, P, a);
 }
 
+// tmg_playout takes peek's dispatch too: peek<...>() launches the playout
+// kernel of the same instantiation
+struct PlayLaunch {
+    dim3 grid;
+    hipStream_t s;
+    const Params &P;
+    const PlayArgs &a;
+    template <int MAXN, bool GEN, int NB, bool CODD>
+    void peek() {
+        const size_t lds = sizeof(Ws<MAXN, GEN>);
+        hipLaunchKernelGGL((playout_kernel<MAXN, GEN, NB, CODD>), grid, dim3(64), lds, s, P, a);
+    }
+};
+
+template <int MAXN>
+void playout_spill_one(hipStream_t s, const Params &P, const PlayArgs &a) {
+    const size_t lds = sizeof(Ws<MAXN, false>);
+    hipLaunchKernelGGL((playout_spill_kernel<MAXN>), dim3(kSpillWaves), dim3(64), lds, s, P, a);
+}
+
 }  // namespace
+
+#if TMG_TU == 13
+void launch_playout_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PlayArgs &a) {
+    PlayLaunch l{grid, s, P, a};
+    peek_lean_ladder(P, maxn, sb, l);
+}
+void launch_playout_spill128(hipStream_t s, const Params &P, const PlayArgs &a) { playout_spill_one<128>(s, P, a); }
+void launch_playout_spill512(hipStream_t s, const Params &P, const PlayArgs &a) { playout_spill_one<512>(s, P, a); }
+#endif
+
+#if TMG_TU == 14
+void launch_playout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PlayArgs &a) {
+    PlayLaunch l{grid, s, P, a};
+    peek_gen_ladder(P, maxn, sb, l);
+}
+#endif
 
 #if TMG_TU == 10
 void launch_rollout_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const RollArgs &a) {
@@ -320,6 +356,10 @@ void launch_rollout_reduce(hipStream_t s, int64_t n, int A, int samples, const i
                            int32_t *best_action, int32_t *best_total) {
     hipLaunchKernelGGL(rollout_reduce_kernel, env_grid(n), dim3(64), 0, s, n, A, samples, ret, total, best_action,
                        best_total);
+}
+void launch_playout_reduce(hipStream_t s, int64_t n, int seqs, const int32_t *ret, int32_t *best_seq,
+                           int32_t *best_ret) {
+    hipLaunchKernelGGL(playout_reduce_kernel, env_grid(n), dim3(64), 0, s, n, seqs, ret, best_seq, best_ret);
 }
 #endif
 

@@ -93,6 +93,19 @@ void launch_rollout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Param
 void launch_rollout_reduce(hipStream_t s, int64_t n, int A, int samples, const int32_t *ret, int32_t *total,
                            int32_t *best_action, int32_t *best_total);
 
+// tmg_playout (tmg_playout.hip): given action sequences played on copies of
+// every env.  grid: env_grid(n * seqs), one wave per virtual env
+struct PlayArgs;
+// TU 13 — lean playout kernels (both families), and the playout spill tier
+void launch_playout_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PlayArgs &a);
+void launch_playout_spill128(hipStream_t s, const Params &P, const PlayArgs &a);
+void launch_playout_spill512(hipStream_t s, const Params &P, const PlayArgs &a);
+// TU 14 — general playout kernels (both families)
+void launch_playout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PlayArgs &a);
+// TU 6 — the best sequence per env (tmg_aux.hip)
+void launch_playout_reduce(hipStream_t s, int64_t n, int seqs, const int32_t *ret, int32_t *best_seq,
+                           int32_t *best_ret);
+
 // tmg_expand_count / tmg_expand (tmg_expand.hip): the child rows of every
 // effective action, counted and placed on the device; the moves themselves
 // are a step launch on those rows (tmg_capi.hip)

@@ -26,9 +26,10 @@ EXPORTS = ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_ste
            "tmg_onehot", "tmg_onehot_channels", "tmg_count_states", "tmg_sample_effective", "tmg_status",
            "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot", "tmg_plan_create", "tmg_plan_config",
            "tmg_plan_step", "tmg_plan_join", "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch",
-           "tmg_graph_destroy", "tmg_peek", "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand")
+           "tmg_graph_destroy", "tmg_peek", "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand",
+           "tmg_playout")
 DTYPE_F32, DTYPE_U8, DTYPE_I32 = 0, 1, 2
-ABI_VERSION = 8
+ABI_VERSION = 9
 SEED_INT, SEED_SPAWN, SEED_STORE_DIRECT, SEED_STORE_STAGED = 0, 1, 0x100, 0x200
 STATUS_INTERNAL, STATUS_OVERFLOW, STATUS_CALLER = 1, 2, 4
 
@@ -106,12 +107,13 @@ def load(path: str = None):
     L.tmg_seed.argtypes = [P, I64, I, P, I, U64, U64, U64, U64, I64, P, P]
     L.tmg_expand_count.argtypes = [P, I64, P, P, P, P, P]
     L.tmg_expand.argtypes = [P, I64, P, P, P, P, P, I, P, I64] + [P] * 10 + [P]
+    L.tmg_playout.argtypes = [P, I64, P, P, I, P, P, I, I, I, P] + [P] * 12 + [P]
     for name in ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_step", "tmg_effective",
                  "tmg_num_actions", "tmg_mask_words", "tmg_abi_version", "tmg_onehot", "tmg_onehot_channels",
                  "tmg_sample_effective", "tmg_status", "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot",
                  "tmg_count_states", "tmg_plan_create", "tmg_plan_config", "tmg_plan_step", "tmg_plan_join",
                  "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy", "tmg_peek",
-                 "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand"):
+                 "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand", "tmg_playout"):
         getattr(L, name).restype = I
     if L.tmg_abi_version() != ABI_VERSION:
         raise TmgError("libtmg.so ABI version mismatch; rebuild it")
@@ -236,6 +238,17 @@ class Context:
         self._check(self._L.tmg_expand(self._h, int(n), board, rng, timer, eff, select, int(trust_eff), first_child,
                                        int(m), child_board, child_rng, child_timer, child_eff, child_parent,
                                        child_action, child_reward, child_n_new, child_n_act, child_flags, stream))
+
+    def playout(self, n, board, rng, rng_per_seq, timer, eff, trust_eff, seqs, depth, actions, ret, n_new, n_act,
+                plies, flags, ply_reward, out_board, out_rng, out_timer, out_eff, best_seq, best_ret, stream):
+        """tmg_playout: the given action sequences ([seqs][n][depth] int32) played on copies of every env,
+        [seqs][n] per output and per final-state array, [n] for best_seq / best_ret (any of them None; the
+        best need ret, out_timer needs timer).  rng: [n][5], or [seqs][n][5] with rng_per_seq.  No input is
+        written.  timer None: no horizon."""
+        self._check(self._L.tmg_playout(self._h, int(n), board, rng, int(bool(rng_per_seq)), timer, eff,
+                                        int(trust_eff), int(seqs), int(depth), actions, ret, n_new, n_act, plies,
+                                        flags, ply_reward, out_board, out_rng, out_timer, out_eff, best_seq,
+                                        best_ret, stream))
 
     def seed(self, m, rng, stream, mode=SEED_INT, seeds=None, seed_words=1, base=0, key0=0, key1=0, period=0):
         """tmg_seed: the PCG64 words of m streams into rng ([m][5] uint64), seeded on the device as numpy

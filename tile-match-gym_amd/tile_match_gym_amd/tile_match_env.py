@@ -430,6 +430,47 @@ class TileMatchEnv(_EnvBase):
         return {"ret": o[0], "plies": o[1], "is_combination_match": (f & _native.FLAG_COMBO) != 0,
                 "shuffled": (f & _native.FLAG_SHUFFLED) != 0}
 
+    def playout(self, sequences) -> dict:
+        """What playing each of the given action sequences from here would
+        return and where it would end, without changing the env (tmg_playout
+        on the host-side board, untrusted mask, the env's own RNG stream and
+        timer).  sequences: Q sequences of action ids, padded to one length
+        with negative ids (a (Q, D) array, or one sequence).  An ineffective
+        action is a move that changes nothing but the timer; a sequence stops
+        at the end of the episode.  numpy arrays with one row per sequence: ret
+        (the summed rewards), num_new_specials, num_specials_activated, plies
+        (int32), ply_reward ((Q, D) int32), is_combination_match, shuffled,
+        done (bool), board ((Q, 2, R, C) int32, the final observation's
+        board) and rng_words ((Q, 5) uint64, the stream position reached)."""
+        if self.timer is None:
+            raise Exception("You must call reset before calling playout")
+        seq = np.ascontiguousarray(np.atleast_2d(np.asarray(sequences)), dtype=np.int32)
+        if seq.ndim != 2 or seq.shape[1] < 1:
+            raise ValueError("sequences must be a (Q, D) array of action ids, D >= 1")
+        if (seq >= self.num_actions).any():
+            raise ValueError(f"action ids must be below {self.num_actions}")
+        Q, D = seq.shape
+        self._upload()
+        self._d_timer.fill_(self.timer)
+        kw = dict(device=self.device)
+        acts = torch.from_numpy(seq).to(self.device)
+        out = torch.zeros((4, Q), dtype=torch.int32, **kw)          # ret, n_new, n_act, plies
+        ply = torch.zeros((Q, D), dtype=torch.int32, **kw)
+        flags = torch.zeros(Q, dtype=torch.uint8, **kw)
+        board = torch.zeros((Q, 2, self.num_rows, self.num_cols), dtype=torch.int8, **kw)
+        rng = torch.zeros((Q, 5), dtype=torch.int64, **kw)
+        self._ctx.playout(1, self._d_board.data_ptr(), self._d_rng.data_ptr(), 0, self._d_timer.data_ptr(), None, 0,
+                          Q, D, acts.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                          out[3].data_ptr(), flags.data_ptr(), ply.data_ptr(), board.data_ptr(), rng.data_ptr(),
+                          None, None, None, None, self._stream())
+        o, f = out.cpu().numpy(), flags.cpu().numpy()
+        if (f & (_native.FLAG_ERROR | _native.FLAG_OVERFLOW)).any():
+            raise _native.TmgError("device reported an error for a played move")
+        return {"ret": o[0], "num_new_specials": o[1], "num_specials_activated": o[2], "plies": o[3],
+                "ply_reward": ply.cpu().numpy(), "is_combination_match": (f & _native.FLAG_COMBO) != 0,
+                "shuffled": (f & _native.FLAG_SHUFFLED) != 0, "done": (f & _native.FLAG_DONE) != 0,
+                "board": board.to(torch.int32).cpu().numpy(), "rng_words": rng.cpu().numpy().view(np.uint64)}
+
     def expand(self) -> dict:
         """The states step(a) would lead to, for every effective action a,
         without changing the env (tmg_expand on the host-side board, the mask

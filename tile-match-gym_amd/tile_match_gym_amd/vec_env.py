@@ -505,6 +505,105 @@ class TileMatchVecEnv:
         self.step_raw(self.actions, fork=fork)
         return out["best_total"]
 
+    _PLAY_OUTPUTS = {"ret": torch.int32, "n_new": torch.int32, "n_act": torch.int32, "plies": torch.int32,
+                     "flags": torch.uint8, "ply_reward": torch.int32}
+
+    def playout(self, actions, rng=None, seed=None, outputs=("ret",), best: bool = False, final: bool = False,
+                horizon: bool = True, first_env: int = 0) -> dict:
+        """Play given action sequences on copies of every env, without changing
+        any state (tmg_playout): row (q, i) is exactly what successive
+        step_raw calls (autoreset off) with actions[q, i, 0], [q, i, 1], ...
+        leave and report on a copy of env i.  actions: a (Q, N, D) int32 device
+        tensor ((N, D): Q = 1).  An ineffective action is a move like any other
+        (reward 0, nothing changes but the timer); a negative action ends its
+        sequence quietly (padding); an action >= A sets FLAG_ERROR, stops the
+        sequence before that ply and raises STATUS_CALLER.  A sequence plays at
+        most min(D, moves left) plies (horizon=False: D plies whatever the timer
+        says; not with final=True) and carries FLAG_DONE when it ends the
+        episode.  outputs: any of "ret", "n_new", "n_act" (the sums over the
+        plies), "plies" ((Q, N) int32), "flags" ((Q, N) uint8: the OR of the
+        plies' flags, plus FLAG_DONE) and "ply_reward" ((Q, N, D) int32);
+        best=True adds "best_seq" / "best_ret" ((N,) int32: the lowest q of
+        maximal ret).  rng=None plays with the envs' own RNG words (shared by
+        all sequences of an env), i.e. with the refills the env will really
+        draw; an (N, 5) int64 device tensor of other PCG64 words is shared the
+        same way, a (Q, N, 5) tensor gives each sequence its own; seed=E draws
+        fresh_rng(Q, E, first_env).  final=True adds "env": a TileMatchVecEnv
+        over the Q * N final states (row q * N + i; autoreset mode "none", mask
+        cache valid, this env's context: close this env last), to peek, roll
+        out, step, expand or play out again.  Joins, then enqueues on the
+        current stream; the output tensors are fresh ones."""
+        self.join()
+        N, dev = self.num_envs, self.board.device
+        if actions.dim() == 2:
+            actions = actions.unsqueeze(0)
+        if actions.dim() != 3 or actions.shape[1] != N or actions.dtype != torch.int32 or actions.device != dev \
+                or not actions.is_contiguous():
+            raise ValueError(f"actions must be a contiguous (Q, {N}, D) int32 tensor on {dev}")
+        Q, D = int(actions.shape[0]), int(actions.shape[2])
+        if Q < 1 or D < 1:
+            raise ValueError("playout needs >= 1 sequence of >= 1 action")
+        for name in outputs:
+            if name not in self._PLAY_OUTPUTS:
+                raise ValueError(f"unknown playout output {name!r}")
+        if final and not horizon:
+            raise ValueError("final=True needs the horizon (the final timers follow the envs')")
+        if rng is not None and seed is not None:
+            raise ValueError("pass rng or seed, not both")
+        if seed is not None:
+            rng = self.fresh_rng(Q, seed, first_env)
+        elif rng is None:
+            rng = self.rng
+        elif tuple(rng.shape) not in ((N, 5), (Q, N, 5)) or rng.dtype != torch.int64 or rng.device != dev \
+                or not rng.is_contiguous():
+            raise ValueError(f"rng must be a contiguous ({N}, 5) or ({Q}, {N}, 5) int64 tensor on {dev}")
+        per_seq = rng.dim() == 3
+        kw = dict(device=dev)
+        names = list(outputs) + (["best_seq", "best_ret"] if best else [])
+        need = set(names) | ({"ret"} if best else set())
+        bufs = {}
+        for name in need:
+            shape = (Q, N, D) if name == "ply_reward" else (N,) if name.startswith("best_") else (Q, N)
+            bufs[name] = torch.empty(shape, dtype=self._PLAY_OUTPUTS.get(name, torch.int32), **kw)
+        fb = fr = ft = fe = None
+        if final:
+            fb = torch.empty((Q * N, 2, self.num_rows, self.num_cols), dtype=torch.int8, **kw)
+            fr = torch.empty((Q * N, 5), dtype=torch.int64, **kw)
+            ft = torch.empty(Q * N, dtype=torch.int32, **kw)
+            fe = torch.empty((Q * N, self.mask_words), dtype=torch.int64, **kw)
+        p = {name: _ptr(bufs.get(name)) for name in ("ret", "n_new", "n_act", "plies", "flags", "ply_reward",
+                                                      "best_seq", "best_ret")}
+        self.ctx.playout(N, _ptr(self.board), _ptr(rng), per_seq, _ptr(self.timer) if horizon else None,
+                         _ptr(self.eff), int(self._eff_valid), Q, D, _ptr(actions), p["ret"], p["n_new"], p["n_act"],
+                         p["plies"], p["flags"], p["ply_reward"], _ptr(fb), _ptr(fr), _ptr(ft), _ptr(fe),
+                         p["best_seq"], p["best_ret"], self._stream())
+        out = {name: bufs[name] for name in names}
+        if final:
+            out["env"] = self._child_env(fb, fr, ft, fe)
+        return out
+
+    def step_best_sequence(self, actions, rng=None, seed=None, horizon: bool = True, first_env: int = 0,
+                           fork: bool = True):
+        """Enqueue one step of the shooting planner: every env plays the first
+        action of its best sequence, actions[best_seq[i], i, 0] (playout(best=
+        True) into self.actions).  Every sequence must start with an action:
+        a first action below 0 (padding only) would leave nothing to play and
+        raises ValueError, checked on the host before anything is enqueued (one
+        wait for the actions tensor).  Arguments as for playout.  Returns that
+        best return (N,) int32."""
+        if actions.dim() == 2:
+            actions = actions.unsqueeze(0)
+        if actions.dim() == 3 and actions.shape[2] > 0 and bool((actions[:, :, 0] < 0).any()):
+            raise ValueError("step_best_sequence needs every sequence to start with an action (>= 0)")
+        out = self.playout(actions, rng=rng, seed=seed, outputs=(), best=True, horizon=horizon, first_env=first_env)
+        idx = out["best_seq"].to(torch.int64)
+        first = actions[:, :, 0].gather(0, idx.unsqueeze(0))[0]
+        if self.actions is None:
+            self.actions = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.actions.copy_(first)
+        self.step_raw(self.actions, fork=fork)
+        return out["best_ret"]
+
     def expand(self, select=None, rng=None, max_children: int = None) -> "Expansion":
         """The successor states of every effective action of every env, without
         changing any state (tmg_expand_count + tmg_expand): one child per (env,

@@ -308,6 +308,20 @@ struct EmuRollout {
     }
 };
 
+// tmg_playout takes peek's dispatch too: peek<...>() runs the playout kernel
+struct EmuPlayout {
+    const tmg::Params &P;
+    const tmg::PlayArgs &a;
+    template <int MAXN, bool GEN, int NB, bool CODD>
+    void peek() {
+        run_blocks(a.n * a.seqs, sizeof(tmg::Ws<MAXN, GEN>), [&] { tmg::playout_kernel<MAXN, GEN, NB, CODD>(P, a); });
+    }
+    template <int MAXN>
+    void spill() {
+        run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<MAXN, false>), [&] { tmg::playout_spill_kernel<MAXN>(P, a); });
+    }
+};
+
 static void emu_do_reset(const tmg::Params &P, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer, uint64_t *eff,
                          const uint8_t *mask, int bits, int epw) {
     EmuReset l{P, n, board, rng, timer, eff, mask, bits, epw};
@@ -445,6 +459,40 @@ int emu_rollout(int R, int C, int k, int smask, int moves, int64_t n, const int8
     g_spill_total += P.spill->total;
     if (total || best_action || best_total)
         run_blocks(n, 0, [&] { tmg::rollout_reduce_kernel(n, P.A, samples, ret, total, best_action, best_total); });
+    return 0;
+}
+
+// tmg_playout without the context and the stream: the same refusals (-1 / -2),
+// peek_ladder on the playout kernels, then (general kernels) the playout spill
+// pass, then the reduce kernel when best_seq or best_ret is asked for.
+int emu_playout(int R, int C, int k, int smask, int moves, int64_t n, const int8_t *board, const uint64_t *rng,
+                int rng_per_seq, const int32_t *timer, const uint64_t *eff, int trust_eff, int seqs, int depth,
+                const int32_t *actions, int32_t *ret, int32_t *n_new, int32_t *n_act, int32_t *plies, uint8_t *flags,
+                int32_t *ply_reward, int8_t *out_board, uint64_t *out_rng, int32_t *out_timer, uint64_t *out_eff,
+                int32_t *best_seq, int32_t *best_ret) {
+    if (!g_jump_init) { tmg::build_jump_table(g_jump); g_jump_init = true; }
+    if (n < 0 || seqs < 1 || depth < 1) return -2;
+    if (n > ((1LL << 26) - 8) / seqs) return -2;
+    if (out_timer && !timer) return -1;
+    if ((best_seq || best_ret) && !ret) return -1;
+    if (reinterpret_cast<uintptr_t>(out_board) & 7) return -2;
+    if (n == 0) return 0;
+    if (!board || !rng || !actions) return -1;
+    if (trust_eff && !eff) return -1;
+    tmg::Params P = make_params(R, C, k, smask, moves, g_jump);
+    P.spill = spill_queue(g_spill_buf, n * seqs);
+    const int maxn = tmg::shape_maxn(P);
+    const bool lean = tmg::lean_step(P, trust_eff);
+    const tmg::PlayArgs a{n, seqs, depth, board, rng, rng_per_seq ? 1 : 0, timer, eff, trust_eff ? 1 : 0, actions,
+                          ret, n_new, n_act, plies, flags, ply_reward, out_board, out_rng, out_timer, out_eff};
+    EmuPlayout S{P, a};
+    tmg::peek_ladder(P, maxn, tmg::shape_sb(P), lean, S);
+    if (!lean) {
+        if (maxn == 128) S.spill<128>();
+        else S.spill<512>();
+    }
+    g_spill_total += P.spill->total;
+    if (best_seq || best_ret) run_blocks(n, 0, [&] { tmg::playout_reduce_kernel(n, seqs, ret, best_seq, best_ret); });
     return 0;
 }
 

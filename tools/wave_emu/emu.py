@@ -33,6 +33,7 @@ def load(asan=False):
     L.emu_peek_route.argtypes = [I, I, I, I, I, P]
     L.emu_rollout.argtypes = [I, I, I, I, I, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32,
                               P, P, P, P, P, P]
+    L.emu_playout.argtypes = [I, I, I, I, I, I64, P, P, I, P, P, I, I, I, P] + [P] * 12
     L.emu_expand_count.argtypes = [I, I, I, I64, P, P, P, P]
     L.emu_expand.argtypes = [I, I, I, I, I, I64, P, P, P, P, P, I, P, I64] + [P] * 10 + [I]
     U64 = ctypes.c_uint64
@@ -122,6 +123,47 @@ def _opt(a, dtype):
 
 def _addr(a):
     return None if a is None else a.ctypes.data
+
+
+PLAYOUT_FIELDS = ("ret", "n_new", "n_act", "plies", "flags", "ply_reward", "out_board", "out_rng", "out_timer",
+                  "out_eff", "best_seq", "best_ret")
+
+
+def playout(L, R, C, k, smask, num_moves, board, rng, timer, eff, trust_eff, actions, fields=PLAYOUT_FIELDS, out=None):
+    """tmg_playout on the emulated kernels: dict of the requested PLAYOUT_FIELDS
+    (ret / n_new / n_act / plies (Q, n) int32, flags (Q, n) uint8, ply_reward
+    (Q, n, D) int32, out_board (Q * n, 2, R, C) int8, out_rng (Q * n, 5) /
+    out_eff (Q * n, W) uint64, out_timer (Q * n,) int32, best_seq / best_ret
+    (n,) int32), freshly allocated with a sentinel fill, or the arrays of `out`
+    (a dict by field name).  actions: (Q, n, D) int32; rng: (n, 5) uint64, or
+    (Q, n, 5) for words per sequence.  The inputs are only read; timer None
+    is no horizon; eff may be None when trust_eff == 0.  A refused call
+    raises ValueError with the return code."""
+    n = board.shape[0]
+    A = 2 * R * C - R - C
+    W = (A + 63) // 64
+    actions = np.ascontiguousarray(actions, dtype=np.int32)
+    Q, _, D = actions.shape
+    assert actions.shape[1] == n
+    board = np.ascontiguousarray(board, dtype=np.int8)
+    rng = np.ascontiguousarray(rng, dtype=np.uint64)
+    assert rng.size in (n * 5, Q * n * 5)
+    per_seq = rng.ndim == 3
+    timer = _opt(timer, np.int32)
+    eff = _opt(eff, np.uint64)
+    if out is None:
+        m = Q * n
+        new = {"ply_reward": np.full((Q, n, D), -7, np.int32), "flags": np.full((Q, n), 0x55, np.uint8),
+               "out_board": np.full((m, 2, R, C), -7, np.int8), "out_rng": np.full((m, 5), 0xA5A5A5A5A5A5A5A5, np.uint64),
+               "out_eff": np.full((m, W), 0xA5A5A5A5A5A5A5A5, np.uint64), "out_timer": np.full(m, -7, np.int32),
+               "best_seq": np.full(n, -7, np.int32), "best_ret": np.full(n, -7, np.int32)}
+        new.update({f: np.full((Q, n), -7, np.int32) for f in ("ret", "n_new", "n_act", "plies")})
+        out = {f: new[f] for f in fields}
+    rc = L.emu_playout(R, C, k, smask, int(num_moves), n, _addr(board), _addr(rng), int(per_seq), _addr(timer),
+                       _addr(eff), int(trust_eff), Q, D, _addr(actions), *(_addr(out.get(f)) for f in PLAYOUT_FIELDS))
+    if rc:
+        raise ValueError(f"emu_playout refused the call ({rc})")
+    return out
 
 
 def expand_count(L, R, C, num_moves, timer, eff, select=None):

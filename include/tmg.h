@@ -245,6 +245,82 @@ TMG_API int tmg_playout(tmg_ctx *ctx, int64_t n, const int8_t *board,
                         int32_t *best_seq, int32_t *best_ret,   /* [n], each or NULL; need ret */
                         void *stream);
 
+/* One move's cascade stage by stage, on copies of every env: what happens
+ * inside Board.move (board.py:330-395).  Row (q, i), for every action row q in
+ * [0, seqs) and env i, traces Board.move(actions[q][i]) on a copy of board[i]
+ * with a copy of rng[i].  Nothing of board, rng, eff or actions is written;
+ * the timer is neither read nor written and TMG_FLAG_DONE is never set, as
+ * for tmg_peek.
+ *   Stages of a move, in order: SWAP; if the move is a combination, COMBO,
+ *     FALL, REFILL; per cascade iteration CLEAR, FALL, REFILL; SHUFFLE when the
+ *     ensure-playable loop shuffled (all its shuffles and row redraws in one
+ *     frame).  A FALL or REFILL that moves or fills nothing is still a stage.
+ *   A stage is recorded when bit (1u << kind) is set in stage_mask.  The f-th
+ *     recorded stage writes frames[q][i][f] (the board after it, both planes),
+ *     kind[q][i][f] and frame_elim[q][i][f]: the reference's count of type-zero
+ *     cells after a COMBO or CLEAR stage (board.py:361, :373), 0 for the other
+ *     kinds.  The first FALL frame of a move, before any draw, is its
+ *     afterstate.
+ *   stop == 0: the move is simulated to its end.  Stages past max_frames are
+ *     not recorded; n_frames counts all stages of the selected kinds, so
+ *     n_frames > max_frames says the trace was cut.  reward / n_new / n_act /
+ *     flags (TMG_FLAG_COMBO | SHUFFLED | ERROR) are exactly tmg_peek's for that
+ *     action and rng, out_rng the words after the move, and the sum of every
+ *     stage's frame_elim plus n_new is reward.
+ *   stop != 0: the row ends right after its max_frames-th recorded frame is
+ *     written and carries TMG_FLAG_STOPPED; n_frames <= max_frames.  reward,
+ *     n_new and n_act cover the stages simulated so far (reward = their
+ *     frame_elim sum + n_new so far), flags holds TMG_FLAG_COMBO once the COMBO
+ *     stage has run and TMG_FLAG_SHUFFLED once the SHUFFLE stage has, out_rng
+ *     the words as those stages left them.  A row whose move ends with fewer
+ *     recorded frames is not stopped and equals the stop == 0 row.
+ *     stage_mask = 1u << TMG_STAGE_FALL, max_frames = 1, stop = 1 is the
+ *     afterstate form: out_rng equals rng[i] (no draw was made) and reward is
+ *     the deterministic part of the move's reward.
+ *   kind / frame_elim entries from min(n_frames, max_frames) on are zeroed;
+ *     frame boards there are not written.
+ *   An ineffective action, as trust_eff defines it, gives zeros, n_frames = 0
+ *     and out_rng = rng[i]; a negative action is quiet padding and gives the
+ *     same.  An action >= A sets TMG_FLAG_ERROR with n_frames = 0 and raises
+ *     TMG_STATUS_CALLER.  trust_eff as tmg_peek: non-zero, eff is this
+ *     library's mask and the first line search is bounded; zero, eff may be
+ *     NULL, the mask is scanned and boards that already hold a line work.
+ *   The general kernels always run (there is no lean precondition): a board
+ *     that holds specials in a no-specials context is traced as the general
+ *     step kernels would step it.  A stage that ends on a safety cap sets
+ *     TMG_FLAG_ERROR, the frames written so far stay valid, and
+ *     TMG_STATUS_INTERNAL is raised.  A row whose cascade outgrows the
+ *     kernels' LDS lists is re-run whole on the worst-case lists, every output
+ *     rewritten, and counts in tmg_spills.
+ *   frames: row (q, i)'s slot f starts at byte ((q * n + i) * max_frames + f)
+ *     * 2 * R * C.  When 2 * R * C is a multiple of 4 the frames are written as
+ *     32-bit words and `frames` must be 4-byte aligned; otherwise they are
+ *     written as bytes, any address works and slots start on 2-byte boundaries.
+ *   Refused: a tmg_create_scan context, n < 0, seqs < 1, max_frames < 1, a
+ *     stage_mask that is zero or has bits outside kinds 1..6, n * seqs above
+ *     2^26 - 8 (one wave each), a null board, rng or actions with n > 0,
+ *     trust_eff != 0 with a null eff, a misaligned frames.  n == 0 is a no-op.
+ *     Asynchronous on `stream`. */
+#define TMG_STAGE_SWAP    1  /* after swap_coords                          board.py:355     */
+#define TMG_STAGE_COMBO   2  /* after combination_match, before gravity    board.py:357-364 */
+#define TMG_STAGE_CLEAR   3  /* after one cascade iteration's resolve: cells cleared,
+                                new specials placed                        board.py:367-376 */
+#define TMG_STAGE_FALL    4  /* after gravity                              board.py:217-229 */
+#define TMG_STAGE_REFILL  5  /* after refill                               board.py:231-241 */
+#define TMG_STAGE_SHUFFLE 6  /* after the whole ensure-playable loop, only when it shuffled:
+                                all its shuffles and row redraws in one frame  board.py:381-391 */
+#define TMG_FLAG_STOPPED  0x10u   /* produced by tmg_trace only */
+TMG_API int tmg_trace(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng /* [n][5] */,
+                      const uint64_t *eff, int trust_eff,
+                      int seqs, const int32_t *actions /* [seqs][n] */,
+                      uint32_t stage_mask, int max_frames, int stop,
+                      int8_t *frames      /* [seqs][n][max_frames][2][R][C] or NULL */,
+                      uint8_t *kind       /* [seqs][n][max_frames] or NULL */,
+                      int32_t *frame_elim /* [seqs][n][max_frames] or NULL */,
+                      int32_t *n_frames   /* [seqs][n] or NULL */,
+                      int32_t *reward, int32_t *n_new, int32_t *n_act, uint8_t *flags /* [seqs][n], each or NULL */,
+                      uint64_t *out_rng   /* [seqs][n][5] or NULL */, void *stream);
+
 /* Successor states of every effective action: the expansion step of a tree
  * search that keeps its children (board, RNG position, timer, mask), to peek,
  * roll out, expand again or score them.  Two calls: tmg_expand_count places

@@ -3262,5 +3262,6 @@ __global__ __launch_bounds__(64) void effective_kernel(Params P, int64_t n, cons
 #include "tmg_peek.hip"
 #include "tmg_rollout.hip"
 #include "tmg_playout.hip"
+#include "tmg_trace.hip"
 
 }  // namespace tmg

@@ -601,6 +601,36 @@ int tmg_playout(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rn
     return hip_check(hipGetLastError(), "kernel launch");
 }
 
+int tmg_trace(tmg_ctx *ctx, int64_t n, const int8_t *board, const uint64_t *rng, const uint64_t *eff, int trust_eff,
+              int seqs, const int32_t *actions, uint32_t stage_mask, int max_frames, int stop, int8_t *frames,
+              uint8_t *kind, int32_t *frame_elim, int32_t *n_frames, int32_t *reward, int32_t *n_new, int32_t *n_act,
+              uint8_t *flags, uint64_t *out_rng, void *stream) {
+    int rc = check_full(ctx, n);
+    if (rc) return rc;
+    if (seqs < 1) return fail(-2, "trace needs >= 1 action row");
+    if (max_frames < 1) return fail(-2, "trace max_frames must be >= 1");
+    if (stage_mask == 0 || (stage_mask & ~0x7Eu)) return fail(-2, "trace stage_mask must select stage kinds 1..6");
+    if (n > kMaxWaveRows / seqs) return fail(-2, "n * seqs is more than one launch holds (2^26 - 8 waves)");
+    // store_board writes a frame as dwords when 2 * R * C is a multiple of 4
+    if ((2 * ctx->P.N) % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3))
+        return fail(-2, "frames must be 4-byte aligned");
+    if (n == 0) return 0;
+    if (!board || !rng || !actions) return fail(-1, "null state or actions buffer");
+    if (trust_eff && !eff) return fail(-1, "trust_eff != 0 needs the effective-action mask");
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int64_t nv = n * seqs;
+    Params P = ctx->P;
+    rc = spill_for(ctx, s, nv, &P.spill, &P.spill_ws);
+    if (rc) return rc;
+    const tmg::TraceArgs a{n, seqs, board, rng, eff, trust_eff ? 1 : 0, actions, stage_mask, max_frames, stop ? 1 : 0,
+                           frames, kind, frame_elim, n_frames, reward, n_new, n_act, flags, out_rng};
+    tmg::launch_trace(ctx->maxn, tmg::env_grid(nv), s, P, a);
+    rc = hip_check(hipGetLastError(), "kernel launch");
+    if (rc) return rc;
+    tmg::launch_trace_spill(ctx->maxn, s, P, a);   // re-run the rows that ran out of LDS list space
+    return hip_check(hipGetLastError(), "kernel launch");
+}
+
 int tmg_expand_count(tmg_ctx *ctx, int64_t n, const int32_t *timer, const uint64_t *eff, const uint64_t *select,
                      int64_t *first_child, void *stream) {
     int rc = check_full(ctx, n);
@@ -954,7 +984,7 @@ __attribute__((visibility("default"))) int tmg_debug_cover(tmg_ctx *ctx, uint64_
 int tmg_num_actions(const tmg_ctx *ctx) { return ctx ? ctx->P.A : -1; }
 int tmg_mask_words(const tmg_ctx *ctx) { return ctx ? ctx->P.W : -1; }
 const char *tmg_last_error(void) { return g_err.c_str(); }
-int tmg_abi_version(void) { return 9; }
+int tmg_abi_version(void) { return 10; }
 const char *tmg_build_info(void) { return "src=" TMG_SRC_SHA ";variant=" TMG_VARIANT; }
 
 }  // extern "C"

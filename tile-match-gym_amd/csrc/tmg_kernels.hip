@@ -1,5 +1,5 @@
 // tmg_kernels.hip — kernel instantiations and their host launchers
-// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..14, so the
+// (tmg_launch.h).  Compiled once per translation unit, TMG_TU = 1..15, so the
 // heavy template instantiations build in parallel; each TU registers only its
 // own kernels.
 #include <hip/hip_runtime.h>
@@ -27,7 +27,7 @@
 #endif
 
 #ifndef TMG_TU
-#error "compile tmg_kernels.hip with -DTMG_TU=1..14"
+#error "compile tmg_kernels.hip with -DTMG_TU=1..15"
 #endif
 
 namespace tmg {
@@ -148,7 +148,30 @@ void playout_spill_one(hipStream_t s, const Params &P, const PlayArgs &a) {
     hipLaunchKernelGGL((playout_spill_kernel<MAXN>), dim3(kSpillWaves), dim3(64), lds, s, P, a);
 }
 
+// tmg_trace: the two general non-bitboard kernels and their spill tier
+template <int MAXN>
+void trace_one(dim3 grid, hipStream_t s, const Params &P, const TraceArgs &a) {
+    const size_t lds = sizeof(Ws<MAXN, true>);
+    hipLaunchKernelGGL((trace_kernel<MAXN>), grid, dim3(64), lds, s, P, a);
+}
+template <int MAXN>
+void trace_spill_one(hipStream_t s, const Params &P, const TraceArgs &a) {
+    const size_t lds = sizeof(Ws<MAXN, false>);
+    hipLaunchKernelGGL((trace_spill_kernel<MAXN>), dim3(kSpillWaves), dim3(64), lds, s, P, a);
+}
+
 }  // namespace
+
+#if TMG_TU == 15
+void launch_trace(int maxn, dim3 grid, hipStream_t s, const Params &P, const TraceArgs &a) {
+    if (maxn == 128) trace_one<128>(grid, s, P, a);
+    else trace_one<512>(grid, s, P, a);
+}
+void launch_trace_spill(int maxn, hipStream_t s, const Params &P, const TraceArgs &a) {
+    if (maxn == 128) trace_spill_one<128>(s, P, a);
+    else trace_spill_one<512>(s, P, a);
+}
+#endif
 
 #if TMG_TU == 13
 void launch_playout_lean(int maxn, bool sb, dim3 grid, hipStream_t s, const Params &P, const PlayArgs &a) {

@@ -106,6 +106,13 @@ void launch_playout_gen(int maxn, bool sb, dim3 grid, hipStream_t s, const Param
 void launch_playout_reduce(hipStream_t s, int64_t n, int seqs, const int32_t *ret, int32_t *best_seq,
                            int32_t *best_ret);
 
+// tmg_trace (tmg_trace.hip): one move's cascade stage by stage on copies of
+// every env.  grid: env_grid(n * seqs), one wave per virtual env
+struct TraceArgs;
+// TU 15 — the general non-bitboard trace kernels (128 / 512 cells) and their spill tier
+void launch_trace(int maxn, dim3 grid, hipStream_t s, const Params &P, const TraceArgs &a);
+void launch_trace_spill(int maxn, hipStream_t s, const Params &P, const TraceArgs &a);
+
 // tmg_expand_count / tmg_expand (tmg_expand.hip): the child rows of every
 // effective action, counted and placed on the device; the moves themselves
 // are a step launch on those rows (tmg_capi.hip)

@@ -27,9 +27,9 @@ EXPORTS = ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_ste
            "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot", "tmg_plan_create", "tmg_plan_config",
            "tmg_plan_step", "tmg_plan_join", "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch",
            "tmg_graph_destroy", "tmg_peek", "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand",
-           "tmg_playout")
+           "tmg_playout", "tmg_trace")
 DTYPE_F32, DTYPE_U8, DTYPE_I32 = 0, 1, 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 SEED_INT, SEED_SPAWN, SEED_STORE_DIRECT, SEED_STORE_STAGED = 0, 1, 0x100, 0x200
 STATUS_INTERNAL, STATUS_OVERFLOW, STATUS_CALLER = 1, 2, 4
 
@@ -45,6 +45,10 @@ COVER_NAMES = ("sb_lean", "sb_normal", "sb_laser", "sb_perp_bomb", "sb_row_bomb"
 
 SPECIAL_BITS = {"cookie": 1, "vertical_laser": 2, "horizontal_laser": 4, "bomb": 8}
 FLAG_DONE, FLAG_COMBO, FLAG_SHUFFLED, FLAG_RESET, FLAG_OVERFLOW, FLAG_ERROR = 1, 2, 4, 8, 0x40, 0x80
+FLAG_STOPPED = 0x10                 # tmg_trace only
+STAGE_SWAP, STAGE_COMBO, STAGE_CLEAR, STAGE_FALL, STAGE_REFILL, STAGE_SHUFFLE = 1, 2, 3, 4, 5, 6
+STAGE_NAMES = {STAGE_SWAP: "swap", STAGE_COMBO: "combo", STAGE_CLEAR: "clear", STAGE_FALL: "fall",
+               STAGE_REFILL: "refill", STAGE_SHUFFLE: "shuffle"}
 
 _libs = {}          # loaded libraries by path
 _M64 = (1 << 64) - 1
@@ -108,12 +112,13 @@ def load(path: str = None):
     L.tmg_expand_count.argtypes = [P, I64, P, P, P, P, P]
     L.tmg_expand.argtypes = [P, I64, P, P, P, P, P, I, P, I64] + [P] * 10 + [P]
     L.tmg_playout.argtypes = [P, I64, P, P, I, P, P, I, I, I, P] + [P] * 12 + [P]
+    L.tmg_trace.argtypes = [P, I64, P, P, P, I, I, P, ctypes.c_uint32, I, I] + [P] * 9 + [P]
     for name in ("tmg_create", "tmg_create_scan", "tmg_destroy", "tmg_reset", "tmg_step", "tmg_effective",
                  "tmg_num_actions", "tmg_mask_words", "tmg_abi_version", "tmg_onehot", "tmg_onehot_channels",
                  "tmg_sample_effective", "tmg_status", "tmg_viable", "tmg_spills", "tmg_step_onehot", "tmg_reset_onehot",
                  "tmg_count_states", "tmg_plan_create", "tmg_plan_config", "tmg_plan_step", "tmg_plan_join",
                  "tmg_plan_destroy", "tmg_plan_capture", "tmg_graph_launch", "tmg_graph_destroy", "tmg_peek",
-                 "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand", "tmg_playout"):
+                 "tmg_rollout", "tmg_seed", "tmg_expand_count", "tmg_expand", "tmg_playout", "tmg_trace"):
         getattr(L, name).restype = I
     if L.tmg_abi_version() != ABI_VERSION:
         raise TmgError("libtmg.so ABI version mismatch; rebuild it")
@@ -249,6 +254,16 @@ class Context:
                                         int(trust_eff), int(seqs), int(depth), actions, ret, n_new, n_act, plies,
                                         flags, ply_reward, out_board, out_rng, out_timer, out_eff, best_seq,
                                         best_ret, stream))
+
+    def trace(self, n, board, rng, eff, trust_eff, seqs, actions, stage_mask, max_frames, stop, frames, kind,
+              frame_elim, n_frames, reward, n_new, n_act, flags, out_rng, stream):
+        """tmg_trace: Board.move(actions[q][i]) ([seqs][n] int32) on a copy of every env, stage by stage:
+        the recorded stages' boards into frames ([seqs][n][max_frames][2][R][C] int8), kinds and
+        eliminations into kind / frame_elim ([seqs][n][max_frames]), [seqs][n] per count, sum and flag,
+        out_rng [seqs][n][5] (any of them None).  No input is written."""
+        self._check(self._L.tmg_trace(self._h, int(n), board, rng, eff, int(trust_eff), int(seqs), actions,
+                                      int(stage_mask), int(max_frames), int(bool(stop)), frames, kind, frame_elim,
+                                      n_frames, reward, n_new, n_act, flags, out_rng, stream))
 
     def seed(self, m, rng, stream, mode=SEED_INT, seeds=None, seed_words=1, base=0, key0=0, key1=0, period=0):
         """tmg_seed: the PCG64 words of m streams into rng ([m][5] uint64), seeded on the device as numpy

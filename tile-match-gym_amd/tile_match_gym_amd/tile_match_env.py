@@ -471,6 +471,52 @@ class TileMatchEnv(_EnvBase):
                 "shuffled": (f & _native.FLAG_SHUFFLED) != 0, "done": (f & _native.FLAG_DONE) != 0,
                 "board": board.to(torch.int32).cpu().numpy(), "rng_words": rng.cpu().numpy().view(np.uint64)}
 
+    def trace(self, action: int, stages=("swap", "combo", "clear", "fall", "refill", "shuffle")):
+        """What step(action) would do to the board, stage by stage, without
+        changing the env (tmg_trace on the host-side board, the mask scanned
+        from it, the env's own RNG stream).  Returns (frames, results): frames
+        is a list of (stage name, int32 board (2, R, C) after that stage,
+        eliminations of that stage), one per stage of the selected kinds in
+        the order the move runs them (an ineffective action has none); results
+        is the step's (num_eliminations, is_combination_match,
+        num_new_specials, num_specials_activated, shuffled)."""
+        if self.timer is None:
+            raise Exception("You must call reset before calling trace")
+        action = int(action)
+        if not 0 <= action < self.num_actions:
+            raise ValueError(f"action ids must be in [0, {self.num_actions})")
+        codes = {name: code for code, name in _native.STAGE_NAMES.items()}
+        mask = 0
+        for name in stages:
+            if name not in codes:
+                raise ValueError(f"unknown trace stage {name!r}")
+            mask |= 1 << codes[name]
+        if not mask:
+            raise ValueError("trace needs at least one stage")
+        self._upload()
+        kw = dict(device=self.device)
+        act = torch.tensor([action], dtype=torch.int32, **kw)
+        F = 64
+        while True:                                  # a cut trace is taken again with room for every frame
+            frames = torch.zeros((F, 2, self.num_rows, self.num_cols), dtype=torch.int8, **kw)
+            kind = torch.zeros(F, dtype=torch.uint8, **kw)
+            elim = torch.zeros(F, dtype=torch.int32, **kw)
+            out = torch.zeros(4, dtype=torch.int32, **kw)            # n_frames, reward, n_new, n_act
+            flags = torch.zeros(1, dtype=torch.uint8, **kw)
+            self._ctx.trace(1, self._d_board.data_ptr(), self._d_rng.data_ptr(), None, 0, 1, act.data_ptr(), mask, F, 0,
+                            frames.data_ptr(), kind.data_ptr(), elim.data_ptr(), out[0:].data_ptr(), out[1:].data_ptr(),
+                            out[2:].data_ptr(), out[3:].data_ptr(), flags.data_ptr(), None, self._stream())
+            o, f = out.cpu().numpy(), int(flags.cpu().numpy()[0])
+            if o[0] <= F:
+                break
+            F = int(o[0])
+        if f & (_native.FLAG_ERROR | _native.FLAG_OVERFLOW):
+            raise _native.TmgError("device reported an error for the traced move")
+        nf = int(o[0])
+        boards, kinds, elims = frames[:nf].to(torch.int32).cpu().numpy(), kind.cpu().numpy(), elim.cpu().numpy()
+        steps = [(_native.STAGE_NAMES[int(kinds[j])], boards[j], int(elims[j])) for j in range(nf)]
+        return steps, (int(o[1]), bool(f & _native.FLAG_COMBO), int(o[2]), int(o[3]), bool(f & _native.FLAG_SHUFFLED))
+
     def expand(self) -> dict:
         """The states step(a) would lead to, for every effective action a,
         without changing the env (tmg_expand on the host-side board, the mask

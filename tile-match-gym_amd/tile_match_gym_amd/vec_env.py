@@ -582,6 +582,88 @@ class TileMatchVecEnv:
             out["env"] = self._child_env(fb, fr, ft, fe)
         return out
 
+    _TRACE_FIELDS = ("frames", "kind", "frame_elim", "n_frames", "reward", "n_new", "n_act", "flags", "out_rng")
+
+    def trace(self, actions, stages=("clear", "fall", "refill"), max_frames: int = 16, stop: bool = False, rng=None,
+              seed=None, frames: bool = True, first_env: int = 0) -> dict:
+        """One move's cascade stage by stage, on copies of every env, without
+        changing any state (tmg_trace): row (q, i) traces Board.move(actions[q,
+        i]) on a copy of env i.  actions: an (N,) or (Q, N) int32 device tensor.
+        stages: the kinds to record, of "swap", "combo", "clear", "fall",
+        "refill", "shuffle" (a move runs swap; combo, fall, refill when it is a
+        combination; clear, fall, refill per cascade iteration; shuffle when the
+        ensure-playable loop shuffled).  Returns "frames" ((Q, N, max_frames, 2,
+        R, C) int8: the board after each recorded stage; None with
+        frames=False), "kind" ((Q, N, max_frames) uint8, 0 past the last
+        frame), "frame_elim" ((Q, N, max_frames) int32: the cells a combo or
+        clear stage emptied), "n_frames", "reward", "n_new", "n_act" ((Q, N)
+        int32), "flags" ((Q, N) uint8) and "out_rng" ((Q, N, 5) int64).
+        stop=False: the move runs to its end, the sums and flags are peek's,
+        n_frames counts every stage of the selected kinds (more than
+        max_frames: the trace was cut) and out_rng holds the words after the
+        move.  stop=True: a row ends right after its max_frames-th frame, with
+        FLAG_STOPPED and the sums, flags and words of the stages run so far.
+        Frame boards past min(n_frames, max_frames) are not written.  An
+        ineffective or negative action gives zeros; an action >= A sets
+        FLAG_ERROR and raises STATUS_CALLER.  rng and seed as for peek.  Joins,
+        then enqueues on the current stream; the output tensors are fresh
+        ones (frames costs Q * N * max_frames * 2RC bytes)."""
+        self.join()
+        N, dev = self.num_envs, self.board.device
+        if actions.dim() == 1:
+            actions = actions.unsqueeze(0)
+        if actions.dim() != 2 or actions.shape[1] != N or actions.dtype != torch.int32 or actions.device != dev \
+                or not actions.is_contiguous():
+            raise ValueError(f"actions must be a contiguous ({N},) or (Q, {N}) int32 tensor on {dev}")
+        Q, F = int(actions.shape[0]), int(max_frames)
+        if Q < 1 or F < 1:
+            raise ValueError("trace needs >= 1 action row and max_frames >= 1")
+        codes = {name: code for code, name in _native.STAGE_NAMES.items()}
+        mask = 0
+        for name in stages:
+            if name not in codes:
+                raise ValueError(f"unknown trace stage {name!r}")
+            mask |= 1 << codes[name]
+        if not mask:
+            raise ValueError("trace needs at least one stage")
+        if rng is not None and seed is not None:
+            raise ValueError("pass rng or seed, not both")
+        if seed is not None:
+            rng = self.fresh_rng(1, seed, first_env)[0]
+        elif rng is None:
+            rng = self.rng
+        elif rng.shape != (N, 5) or rng.dtype != torch.int64 or rng.device != dev or not rng.is_contiguous():
+            raise ValueError(f"rng must be a contiguous ({N}, 5) int64 tensor on {dev}")
+        kw = dict(device=dev)
+        out = {"frames": torch.empty((Q, N, F, 2, self.num_rows, self.num_cols), dtype=torch.int8, **kw) if frames
+               else None,
+               "kind": torch.empty((Q, N, F), dtype=torch.uint8, **kw),
+               "frame_elim": torch.empty((Q, N, F), dtype=torch.int32, **kw),
+               "flags": torch.empty((Q, N), dtype=torch.uint8, **kw),
+               "out_rng": torch.empty((Q, N, 5), dtype=torch.int64, **kw)}
+        for name in ("n_frames", "reward", "n_new", "n_act"):
+            out[name] = torch.empty((Q, N), dtype=torch.int32, **kw)
+        self.ctx.trace(N, _ptr(self.board), _ptr(rng), _ptr(self.eff), int(self._eff_valid), Q, _ptr(actions), mask, F,
+                       bool(stop), *(_ptr(out[name]) for name in self._TRACE_FIELDS), self._stream())
+        return out
+
+    def afterstates(self, actions=None):
+        """The afterstate of every traced action: the board at the end of the
+        move's deterministic prefix (the swap, the first resolve, the first
+        gravity), holes at the top and no draw made yet, which is what
+        afterstate value functions and chance-node search work on.  actions: as
+        for trace; None is every action, Q = A.  Returns (boards (Q, N, 2, R, C)
+        int8, reward (Q, N) int32: the deterministic part of the move's reward,
+        effective (Q, N) bool).  The board of an ineffective action is the
+        env's own.  Costs Q * N * 2RC bytes: N * A * 2RC for every action."""
+        N, A = self.num_envs, self.num_actions
+        if actions is None:
+            actions = torch.arange(A, dtype=torch.int32, device=self.board.device).unsqueeze(1).expand(A, N).contiguous()
+        out = self.trace(actions, stages=("fall",), max_frames=1, stop=True)
+        effective = out["n_frames"] > 0
+        boards = torch.where(effective[:, :, None, None, None], out["frames"][:, :, 0], self.board.unsqueeze(0))
+        return boards, out["reward"], effective
+
     def step_best_sequence(self, actions, rng=None, seed=None, horizon: bool = True, first_env: int = 0,
                            fork: bool = True):
         """Enqueue one step of the shooting planner: every env plays the first

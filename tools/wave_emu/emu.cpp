@@ -496,6 +496,37 @@ int emu_playout(int R, int C, int k, int smask, int moves, int64_t n, const int8
     return 0;
 }
 
+// tmg_trace without the context and the stream: the same refusals (-1 / -2),
+// the general non-bitboard trace kernel of the shape's size class, then its
+// spill pass.
+int emu_trace(int R, int C, int k, int smask, int64_t n, const int8_t *board, const uint64_t *rng, const uint64_t *eff,
+              int trust_eff, int seqs, const int32_t *actions, uint32_t stage_mask, int max_frames, int stop,
+              int8_t *frames, uint8_t *kind, int32_t *frame_elim, int32_t *n_frames, int32_t *reward, int32_t *n_new,
+              int32_t *n_act, uint8_t *flags, uint64_t *out_rng) {
+    if (!g_jump_init) { tmg::build_jump_table(g_jump); g_jump_init = true; }
+    if (n < 0 || seqs < 1 || max_frames < 1) return -2;
+    if (stage_mask == 0 || (stage_mask & ~0x7Eu)) return -2;
+    if (n > ((1LL << 26) - 8) / seqs) return -2;
+    if ((2 * R * C) % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3)) return -2;
+    if (n == 0) return 0;
+    if (!board || !rng || !actions) return -1;
+    if (trust_eff && !eff) return -1;
+    tmg::Params P = make_params(R, C, k, smask, 1, g_jump);
+    P.spill = spill_queue(g_spill_buf, n * seqs);
+    const int maxn = tmg::shape_maxn(P);
+    const tmg::TraceArgs a{n, seqs, board, rng, eff, trust_eff ? 1 : 0, actions, stage_mask, max_frames, stop ? 1 : 0,
+                           frames, kind, frame_elim, n_frames, reward, n_new, n_act, flags, out_rng};
+    if (maxn == 128) {
+        run_blocks(n * seqs, sizeof(tmg::Ws<128, true>), [&] { tmg::trace_kernel<128>(P, a); });
+        run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<128, false>), [&] { tmg::trace_spill_kernel<128>(P, a); });
+    } else {
+        run_blocks(n * seqs, sizeof(tmg::Ws<512, true>), [&] { tmg::trace_kernel<512>(P, a); });
+        run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<512, false>), [&] { tmg::trace_spill_kernel<512>(P, a); });
+    }
+    g_spill_total += P.spill->total;
+    return 0;
+}
+
 // tmg_expand_count without the context and the stream: the three launches of
 // expand_count_kernel (csrc/tmg_expand.hip), one wave per tile of envs
 int emu_expand_count(int R, int C, int moves, int64_t n, const int32_t *timer, const uint64_t *eff,

@@ -34,6 +34,7 @@ def load(asan=False):
     L.emu_rollout.argtypes = [I, I, I, I, I, I64, P, P, P, P, I, I, I, ctypes.c_uint64, I64, ctypes.c_int32,
                               P, P, P, P, P, P]
     L.emu_playout.argtypes = [I, I, I, I, I, I64, P, P, I, P, P, I, I, I, P] + [P] * 12
+    L.emu_trace.argtypes = [I, I, I, I, I64, P, P, P, I, I, P, ctypes.c_uint32, I, I] + [P] * 9
     L.emu_expand_count.argtypes = [I, I, I, I64, P, P, P, P]
     L.emu_expand.argtypes = [I, I, I, I, I, I64, P, P, P, P, P, I, P, I64] + [P] * 10 + [I]
     U64 = ctypes.c_uint64
@@ -163,6 +164,40 @@ def playout(L, R, C, k, smask, num_moves, board, rng, timer, eff, trust_eff, act
                        _addr(eff), int(trust_eff), Q, D, _addr(actions), *(_addr(out.get(f)) for f in PLAYOUT_FIELDS))
     if rc:
         raise ValueError(f"emu_playout refused the call ({rc})")
+    return out
+
+
+TRACE_FIELDS = ("frames", "kind", "frame_elim", "n_frames", "reward", "n_new", "n_act", "flags", "out_rng")
+
+
+def trace(L, R, C, k, smask, board, rng, eff, trust_eff, actions, stage_mask, max_frames, stop=0, fields=TRACE_FIELDS,
+          out=None):
+    """tmg_trace on the emulated kernels: dict of the requested TRACE_FIELDS
+    (frames (Q, n, F, 2, R, C) int8, kind (Q, n, F) uint8, frame_elim (Q, n, F)
+    int32, n_frames / reward / n_new / n_act (Q, n) int32, flags (Q, n) uint8,
+    out_rng (Q, n, 5) uint64), freshly allocated with a sentinel fill, or the
+    arrays of `out` (a dict by field name).  actions: (Q, n) int32.  The inputs
+    are only read; eff may be None when trust_eff == 0.  A refused call raises
+    ValueError with the return code."""
+    n = board.shape[0]
+    actions = np.ascontiguousarray(actions, dtype=np.int32)
+    Q = actions.shape[0]
+    assert actions.shape == (Q, n)
+    board = np.ascontiguousarray(board, dtype=np.int8)
+    rng = np.ascontiguousarray(rng, dtype=np.uint64)
+    assert rng.size == n * 5
+    eff = _opt(eff, np.uint64)
+    F = int(max_frames)
+    if out is None:
+        new = {"frames": np.full((Q, n, max(F, 0), 2, R, C), -7, np.int8), "kind": np.full((Q, n, max(F, 0)), 0x55, np.uint8),
+               "frame_elim": np.full((Q, n, max(F, 0)), -7, np.int32), "flags": np.full((Q, n), 0x55, np.uint8),
+               "out_rng": np.full((Q, n, 5), 0xA5A5A5A5A5A5A5A5, np.uint64)}
+        new.update({f: np.full((Q, n), -7, np.int32) for f in ("n_frames", "reward", "n_new", "n_act")})
+        out = {f: new[f] for f in fields}
+    rc = L.emu_trace(R, C, k, smask, n, _addr(board), _addr(rng), _addr(eff), int(trust_eff), Q, _addr(actions),
+                     int(stage_mask), F, int(stop), *(_addr(out.get(f)) for f in TRACE_FIELDS))
+    if rc:
+        raise ValueError(f"emu_trace refused the call ({rc})")
     return out
 
 

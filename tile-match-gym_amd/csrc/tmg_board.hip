@@ -155,6 +155,11 @@ enum : int {
     CV_ROLL_SPILL_RUN,   // tmg_rollout: virtual env re-run by rollout_spill_kernel
     CV_BP_PAIR_ACC,      // bp_redraw_pairs: the round's second redraw taken from a guessed lane group
     CV_BP_PAIR_REJ,      // bp_redraw_pairs: no lane group had guessed the second redraw's rows
+    CV_RP_VSHIFT,        // rp_move: the first line's vertical runs moved three rows in the first gravity pass
+    CV_RP_VMORE,         // rp_move: passes were still needed after the three-row shift
+    CV_RP_SCAN2,         // rp_scan: the final scan ran on the planes of colour - 1 (scan_rows_core's EDGE)
+    CV_BP_ROUND_CARRY,   // bp_redraw_pairs: a rejected round's second redraw carried over as the next round's first
+    CV_RP_NOLDS,         // rp_move: the closing LDS write left out, an inline regeneration rewrites the board
     CV_COUNT = 48
 };
 #if TMG_COVER
@@ -932,7 +937,15 @@ __device__ __forceinline__ void lds_row(const WS &w, int off, int nd, uint32_t (
 // masked to the row's columns cm) and, with specials, its type masks NS / CK /
 // Z.  scan_rows_nb reads them from the LDS board; the row-plane cascade
 // (tmg_rp.hip) hands over the planes it already holds.
-template <bool TYPES, int NBV, class WS>
+// EDGE (the row-plane cascade, rp_scan, where it saves a plane): X holds planes
+// of colour - 1 instead, in which a cell outside the board reads as colour 1;
+// "outside differs from every tile" is then ORed into each D mask as the
+// columns where one of its two cells lies outside the board (O: constants per
+// shift in the shape-specialised kernels; a lane off the board and the rows
+// r+1..r+3 beyond R give all ones).  Every bit of a D mask that reaches mv or
+// mh compares a cell with one of the action's own two cells, which is inside,
+// so "both outside" (0 in the colour-value planes, 1 here) is never looked at.
+template <bool TYPES, int NBV, bool EDGE = false, class WS>
 __device__ __forceinline__ int scan_rows_core(const Params &P, WS &w, int lane_, int r, bool clean, const uint32_t (&X)[NBV],
                                               uint32_t cm, uint32_t NS, uint32_t CK, uint32_t Z, bool odd) {
     const int R = P.R, C = P.C;
@@ -955,17 +968,23 @@ __device__ __forceinline__ int scan_rows_core(const Params &P, WS &w, int lane_,
         }
         return m;
     };
+    // EDGE: columns where (r + dr, c + sx) or (r, c + sy) lies outside the board
+    const auto O = [&](int dr, int sx, int sy) -> uint32_t {
+        if constexpr (!EDGE) return 0u;
+        const uint32_t x = r + dr < R ? cm : 0u;
+        return ~((sx >= 0 ? x >> sx : x << -sx) & (cm >> sy));
+    };
     // the D masks (bit c: the two cells named differ)
-    const uint32_t E1 = D(X1, -1, X, 0);      // (r+1, c-1) vs (r, c)
-    const uint32_t E2 = D(X1, -2, X, 0);      // (r+1, c-2) vs (r, c)
-    const uint32_t F1 = D(X1, 1, X, 0);       // (r+1, c+1) vs (r, c)
-    const uint32_t F2 = D(X1, 2, X, 0);       // (r+1, c+2) vs (r, c)
-    const uint32_t V2d = D(X2, 0, X, 0);      // (r+2, c) vs (r, c)
-    const uint32_t V3d = D(X3, 0, X, 0);      // (r+3, c) vs (r, c)
-    const uint32_t G2 = D(X, 2, X, 0);        // (r, c+2) vs (r, c)
-    const uint32_t G3 = D(X, 3, X, 0);        // (r, c+3) vs (r, c)
-    const uint32_t W2 = D(X2, 1, X, 0);       // (r+2, c+1) vs (r, c)
-    const uint32_t Dn2 = D(X2, 0, X, 1);      // (r+2, c) vs (r, c+1)
+    const uint32_t E1 = D(X1, -1, X, 0) | O(1, -1, 0);    // (r+1, c-1) vs (r, c)
+    const uint32_t E2 = D(X1, -2, X, 0) | O(1, -2, 0);    // (r+1, c-2) vs (r, c)
+    const uint32_t F1 = D(X1, 1, X, 0) | O(1, 1, 0);      // (r+1, c+1) vs (r, c)
+    const uint32_t F2 = D(X1, 2, X, 0) | O(1, 2, 0);      // (r+1, c+2) vs (r, c)
+    const uint32_t V2d = D(X2, 0, X, 0) | O(2, 0, 0);     // (r+2, c) vs (r, c)
+    const uint32_t V3d = D(X3, 0, X, 0) | O(3, 0, 0);     // (r+3, c) vs (r, c)
+    const uint32_t G2 = D(X, 2, X, 0) | O(0, 2, 0);       // (r, c+2) vs (r, c)
+    const uint32_t G3 = D(X, 3, X, 0) | O(0, 3, 0);       // (r, c+3) vs (r, c)
+    const uint32_t W2 = D(X2, 1, X, 0) | O(2, 1, 0);      // (r+2, c+1) vs (r, c)
+    const uint32_t Dn2 = D(X2, 0, X, 1) | O(2, 0, 1);     // (r+2, c) vs (r, c+1)
     // the same pairs seen from lanes above (off the board: all ones = differ)
     const uint32_t A = from_prev_lane(V2d, ~0u);                       // (r-1, c) vs (r+1, c)
     const uint32_t B = from_prev_lane(from_prev_lane(V3d, ~0u), ~0u);  // (r-2, c) vs (r+1, c)
@@ -1781,6 +1800,32 @@ __device__ __forceinline__ uint32_t bp_merge(uint32_t m, uint32_t v, uint32_t ol
 #endif
 }
 
+// TMG_BP_ROUND: A/B switch of the round (0: every round fills the ring first and
+// reads both redraws' dwords).  1: (a) the dwords of a rejected round's second
+// redraw, read and aligned into v2[], are the next round's first redraw (its
+// offset is the consume position the rejection leaves) and are carried over in
+// registers instead of read again; (b) the round's 2 N colours are filled
+// before the round begins, its reads are issued first and the ring is then
+// filled while fewer than 4 N are ahead, so the fill's multiply chain, ballots
+// and stores run while the reads are in flight.  The fill never reaches the
+// dwords of the round: fewer than 4 N + 128 <= kBpMaxAhead colours are ahead of
+// the consume position, the ring holds 1 024.  (c) rp_move leaves out its
+// closing bp_to_lds where an inline regeneration rewrites the board (step_env).
+// The colours consumed and their order are unchanged.
+// The value is a set of bits, one per part: 1 (a), 2 (b), 4 (c).  The library
+// builds none of them (0): with all three the c2 line measured 1.2 % below the
+// parent and the storm's wave-cycles 3.4 % above; with (b) the
+// round's eight ring dwords are live across the fill's 128-bit multiply, and
+// the two kernels that run this loop, the shape-specialised 10x10 step and
+// reset kernels, take 8 and 16 bytes of scratch at their 64 VGPRs.  The
+// TMG_COVER build carries (a) and (c) (5), for the device tests of the round;
+// the host wave emulator builds all three (7).
+#ifndef TMG_BP_ROUND
+#define TMG_BP_ROUND 0
+#endif
+#define TMG_BPR_CARRY ((TMG_BP_ROUND & 1) != 0)
+#define TMG_BPR_FILL ((TMG_BP_ROUND & 2) != 0)
+#define TMG_BPR_NOLDS ((TMG_BP_ROUND & 4) != 0)
 // remove_colour_lines' redraws (board.py:120-131), two per round where a guess
 // holds.  pl: the board, the same in every lane group, on entry and on return.
 template <int NB, class WS>
@@ -1798,44 +1843,75 @@ __device__ __forceinline__ void bp_redraw_pairs(const Params &P, WS &w, int lane
     const int rlC = rl * C;
     const int glC = grp ? (rl + 2 - grp) * C : 0x10000;
     const int ahead = 2 * P.N;                                         // both redraws' colours, <= 256
+    static_assert(4 * 128 + 128 <= kBpMaxAhead, "TMG_BP_ROUND fills while fewer than 4 N are ahead (N <= 128)");
     const uint32_t *ring = bp_ring(w);
     // the ring's counters said uniform once, here: through the rounds they then stay in SGPRs
     r.fill = __builtin_amdgcn_readfirstlane(r.fill);
     r.cons = __builtin_amdgcn_readfirstlane(r.cons);
     int r0 = bp_group_line_row(bp_search_groups<NB>(pl, hml, vml), 0);
+    uint32_t v2[NB];
+    bool carried = false;                                              // wave-uniform: v2[] holds this round's redraw 1
+#pragma unroll
+    for (int b = 0; b < NB; b++) v2[b] = 0u;
+#if TMG_BPR_FILL
+    if (r0 >= 0) {                                                     // the first round's colours
+        while (r.fill - r.cons < ahead) bp_ring_fill<NB>(P, w, lane, J, r);
+    }
+#endif
     while (r0 >= 0) {
         const int row = R - 1 < r0 + 1 ? R - 1 : r0 + 1;              // redraw 1: rows 0..row (rho)
         const int s1 = (row + 1) * C;
+#if !TMG_BPR_FILL
         while (r.fill - r.cons < ahead) bp_ring_fill<NB>(P, w, lane, J, r);
+#endif
         WFENCE();                                                      // as bp_prefetch
         const int o1 = r.cons + rlC, o2 = o1 + s1;
         const int d1 = (o1 >> 5) & (kBpRingDw - 1), d2 = (o2 >> 5) & (kBpRingDw - 1);
         uint32_t lo1[NB], hi1[NB], lo2[NB], hi2[NB];
+        if (!carried) {
+#pragma unroll
+            for (int b = 0; b < NB; b++) {
+                lo1[b] = ring[b * kBpPlaneDw + d1];
+                hi1[b] = ring[b * kBpPlaneDw + d1 + 1];
+            }
+        } else {
+            COVER(CV_BP_ROUND_CARRY);
+#pragma unroll
+            for (int b = 0; b < NB; b++) lo1[b] = hi1[b] = 0u;
+        }
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            lo1[b] = ring[b * kBpPlaneDw + d1];
-            hi1[b] = ring[b * kBpPlaneDw + d1 + 1];
             lo2[b] = ring[b * kBpPlaneDw + d2];
             hi2[b] = ring[b * kBpPlaneDw + d2 + 1];
         }
+#if TMG_BPR_FILL
+        // the round's colours were filled before it began (ahead >= 2 N at the
+        // loop top); the colours of the next one, while these reads are in flight
+        WFENCE();
+        while (r.fill - r.cons < 2 * ahead) bp_ring_fill<NB>(P, w, lane, J, r);
+#endif
         const uint32_t in1 = rlC < s1 ? cm : 0u;
         const uint32_t in2 = glC < s1 ? cm : 0u;
         RowPlanes<NB> pg;                                              // redraw 1, then this group's guess
-        uint32_t v2[NB];
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            const uint32_t v1 = __builtin_amdgcn_alignbit(hi1[b], lo1[b], (uint32_t)o1 & 31u);
+            const uint32_t v1 = carried ? v2[b] : __builtin_amdgcn_alignbit(hi1[b], lo1[b], (uint32_t)o1 & 31u);
             v2[b] = __builtin_amdgcn_alignbit(hi2[b], lo2[b], (uint32_t)o2 & 31u);
             pl.p[b] = bp_merge(in1, v1, pl.p[b]);
             pg.p[b] = bp_merge(in2, v2[b], pl.p[b]);
         }
+        carried = false;
         r.cons += s1;
         const BpLines s = bp_search_groups<NB>(pg, hml, vml);
         r0 = bp_group_line_row(s, 0);
         if (r0 < 0) break;
         const int row2 = R - 1 < r0 + 1 ? R - 1 : r0 + 1;             // redraw 2: rows 0..row2 (rho')
         const int g = row2 - row + 2;
-        if (g < 1 || g > 3) { COVER(CV_BP_PAIR_REJ); continue; }     // not guessed: redraw 2 opens the next round
+        if (g < 1 || g > 3) {                                         // not guessed: redraw 2 opens the next round
+            COVER(CV_BP_PAIR_REJ);
+            carried = TMG_BPR_CARRY;                                  // at o2, where v2[] was read
+            continue;
+        }
         COVER(CV_BP_PAIR_ACC);
         r0 = bp_group_line_row(s, g);
         const int s2 = (row2 + 1) * C;
@@ -2973,7 +3049,13 @@ __device__ __forceinline__ uint32_t step_env(
     bool changed = false;
     if (effective) {
         if constexpr (SBNB > 0 && !GEN) {
-            if (rowp) elim = rp_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags);
+            // an inline regeneration follows and nothing reads the final board
+            // (vo_final, the fused outputs): bp_generate rewrites the whole LDS
+            // board, sb_generate_exact after it where a word was rejected
+            bool nolds = false;
+            if constexpr (INLINE_GEN)
+                nolds = regen && regen_inline && P.C <= 32 && !P.vo_final && !P.oh && !P.vo_obs;
+            if (rowp) elim = rp_move<SBNB, CODD, kRpLevers>(P, w, lane, J, g, cl, p1, p2, flags, nolds);
             else elim = sb_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags, e);
         } else elim = board_move<MAXN, GEN, SBNB, CODD, TIER>(P, w, lane, J, g, cl, p1, p2, flags, nn, na, e, lists,
                                                              trust_eff != 0);

@@ -95,10 +95,17 @@ __device__ __forceinline__ int rp_scan_nb(const Params &P, WS &w, int lane, cons
     }
     return scan_rows_core<false, NBV>(P, w, lane, lane, true, X, cm, 0u, 0u, 0u, false);
 }
-template <int NB, class WS>
+// SCAN2: where the colour value needs a plane more than colour - 1 (k = 2, 4,
+// 8: NB = sb_planes(k)), the scan runs on the NB planes as they are, the board's
+// edge ORed into its D masks (scan_rows_core's EDGE)
+template <int NB, bool SCAN2, class WS>
 __device__ __forceinline__ int rp_scan(const Params &P, WS &w, int lane, const RowPlanes<NB> &pl, uint32_t cm) {
     constexpr int NB1 = NB < 4 ? NB + 1 : 4;
     if (rs_planes(P.k) == NB) return rp_scan_nb<NB, NB>(P, w, lane, pl, cm);
+    if constexpr (SCAN2) {
+        COVER(CV_RP_SCAN2);
+        return scan_rows_core<false, NB, true>(P, w, lane, lane, true, pl.p, cm, 0u, 0u, 0u, false);
+    }
     return rp_scan_nb<NB, NB1>(P, w, lane, pl, cm);
 }
 
@@ -115,6 +122,26 @@ __device__ __forceinline__ uint32_t rp_slice(uint64_t lo, uint64_t hi, int s, bo
 #ifndef TMG_RP_BATCH
 #define TMG_RP_BATCH 1
 #endif
+
+// TMG_RP_VSHIFT: A/B switch (0: gravity moves every column one row per pass;
+// 1: the columns of the first line's vertical runs move three rows in the
+// first pass, rp_move)
+#ifndef TMG_RP_VSHIFT
+#define TMG_RP_VSHIFT 1
+#endif
+// TMG_RP_SCAN2: A/B switch (0: the final effective-mask scan on planes of the
+// colour value, rp_scan_nb; 1: on the cascade's own planes of colour - 1 where
+// those are one fewer, rp_scan)
+#ifndef TMG_RP_SCAN2
+#define TMG_RP_SCAN2 1
+#endif
+// The two levers are arguments of rp_move (LV), handed over by the lean step
+// (step_env) alone: tmg_peek, tmg_rollout and tmg_playout call rp_move without
+// them and keep their object code.
+// RP_NOLDS (TMG_BP_ROUND, tmg_board.hip): the caller may say that the final
+// board is not needed in LDS (an inline regeneration rewrites all of it).
+enum : int { RP_VSHIFT = 1, RP_SCAN2 = 2, RP_NOLDS = 4 };
+constexpr int kRpLevers = (TMG_RP_VSHIFT ? RP_VSHIFT : 0) | (TMG_RP_SCAN2 ? RP_SCAN2 : 0) | (TMG_BPR_NOLDS ? RP_NOLDS : 0);
 
 // Lemire rejection among the T colours of a refill: exact serial replay, cell
 // by cell, from the exact stream position g
@@ -372,10 +399,12 @@ __device__ __forceinline__ void rp_take(const Params &P, WS &w, int lane, RpBatc
 // planes — the effectiveness test (:352) is the caller's.  J: the jump-table
 // row of output bp_out(lane) (rp_batch).  Returns eliminations; leaves the
 // final board in LDS and its effective mask in w.effw.
-template <int NB, bool CODD, class WS>
+template <int NB, bool CODD, int LV = 0, class WS>
 __device__ __forceinline__ int rp_move(const Params &P, WS &w, int lane, const LaneJump &J, Rng &g,
-                                       const Cells<WS::NP> &cl, int p1, int p2, int &flags) {
+                                       const Cells<WS::NP> &cl, int p1, int p2, int &flags, bool nolds = false) {
     const int R = P.R, C = P.C;
+    if constexpr (!(LV & RP_NOLDS)) nolds = false;
+    constexpr bool VSHIFT = (LV & RP_VSHIFT) != 0, SCAN2 = (LV & RP_SCAN2) != 0;
     int8_t *col = w.brd;
 #if TMG_RP_BATCH
     // Every move that gets here clears a line (the cached mask said so, or
@@ -445,14 +474,41 @@ __device__ __forceinline__ int rp_move(const Params &P, WS &w, int lane, const L
         // rows at and above the lowest one down by one; the row shifted in at
         // the top is a cell to refill (G)
         uint32_t E = clr, G = 0u;
-        for (int pass = 0;; pass++) {
+        int pass = 0;
+        // VSHIFT: a column of vv holds a run of >= 3 cleared cells ending at row rs and
+        // no hole below it (rs is the bottom-most row of any line, and every
+        // cleared cell lies in a row <= rs), so the loop's first three passes
+        // there all find the lowest hole at row rs: rows <= rs take the row
+        // three up, at once.  vv and rs are wave-uniform: no scan over lanes
+        // for these columns.  Every other column makes its first pass as in
+        // the loop; the loop finishes what E still holds (runs longer than 3,
+        // a second hole above a run, two separate holes in a column).
+        bool settle = true;
+        if (VSHIFT && vv) {
+            COVER(CV_RP_PASSES);                         // the loop would have needed >= 3 passes
+            COVER(CV_RP_VSHIFT);
             const uint32_t M = rp_or_below(E);
+            const uint32_t Mv = lane <= rs ? vv : 0u, M1 = M & ~Mv;      // Mv | M1 == M
 #pragma unroll
-            for (int b = 0; b < NB; b++) pl.p[b] = (rp_dn<1>(pl.p[b], 0u) & M) | (pl.p[b] & ~M);
-            E = (rp_dn<1>(E, 0u) & M) | (E & ~M);
-            G = (rp_dn<1>(G, ~0u) & M) | (G & ~M);
-            if (__ballot(E != 0u) == 0ULL) break;
-            if (pass == 0) COVER(CV_RP_PASSES);
+            for (int b = 0; b < NB; b++)
+                pl.p[b] = (rp_dn<3>(pl.p[b], 0u) & Mv) | (rp_dn<1>(pl.p[b], 0u) & M1) | (pl.p[b] & ~M);
+            E = (rp_dn<3>(E, 0u) & Mv) | (rp_dn<1>(E, 0u) & M1) | (E & ~M);
+            G = (rp_dn<3>(0u, ~0u) & Mv) | (rp_dn<1>(0u, ~0u) & M1);
+            pass = 1;
+            settle = __ballot(E != 0u) != 0ULL;
+            if (settle) COVER(CV_RP_VMORE);
+        }
+        if (settle) {
+            for (;; pass++) {
+                const uint32_t M = rp_or_below(E);
+#pragma unroll
+                for (int b = 0; b < NB; b++) pl.p[b] = (rp_dn<1>(pl.p[b], 0u) & M) | (pl.p[b] & ~M);
+                E = (rp_dn<1>(E, 0u) & M) | (E & ~M);
+                G = (rp_dn<1>(G, ~0u) & M) | (G & ~M);
+                if (__ballot(E != 0u) == 0ULL) break;
+                // after a three-row shift pass starts at 1: that iteration was counted above
+                if (pass == 0) COVER(CV_RP_PASSES);
+            }
         }
         // refill (:233-241): row-major draw order
         const int n = __builtin_popcount(G);
@@ -469,9 +525,14 @@ __device__ __forceinline__ int rp_move(const Params &P, WS &w, int lane, const L
 #endif
     // :381-391, from the planes: the effective mask of the final board; the
     // board to LDS for the write-back; the rare shuffle on the scalar bitboards
-    const int any = rp_scan<NB>(P, w, lane, pl, cm);
-    bp_to_lds<NB>(P, w, lane, pl);
-    WSYNC();
+    const int any = rp_scan<NB, SCAN2>(P, w, lane, pl, cm);
+    // nolds: the board goes to LDS only for the rare shuffle below
+    if (!nolds || !any) {
+        bp_to_lds<NB>(P, w, lane, pl);
+        WSYNC();
+    } else {
+        COVER(CV_RP_NOLDS);
+    }
     if (!any) {
         const LaneJump Jl = load_jump(P, lane, g);
         SBC c = sb_codes_from_lds(P, w.brd, lane);

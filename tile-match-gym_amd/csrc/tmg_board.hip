@@ -160,7 +160,9 @@ enum : int {
     CV_RP_SCAN2,         // rp_scan: the final scan ran on the planes of colour - 1 (scan_rows_core's EDGE)
     CV_BP_ROUND_CARRY,   // bp_redraw_pairs: a rejected round's second redraw carried over as the next round's first
     CV_RP_NOLDS,         // rp_move: the closing LDS write left out, an inline regeneration rewrites the board
-    CV_COUNT = 48
+    CV_PLAIN_EXIT,       // plain_step_kernel: the ineffective-move exit taken
+    CV_PLAIN_STEP,       // plain_step_kernel: the wave went on into step_env
+    CV_COUNT = 50
 };
 #if TMG_COVER
 #define COVER(site)                                                                                     \
@@ -2873,6 +2875,39 @@ __device__ __forceinline__ void store_rng(uint64_t *p, const Rng &g, int lane) {
 
 #include "tmg_rp.hip"
 
+// ---- the plain step (plain_step_kernel below; plain_step, tmg_dispatch.h)
+// What its prologue hands step_env: the action, the timer before the step,
+// the launch's num_moves and the action's bit of the cached mask.
+struct PlainPre {
+    int a, t0, num_moves;
+    bool effective;
+};
+// Env e's row of a per-env array of `per` elements a row, by a 32-bit byte
+// offset: one s_mul_i32 and a 64-bit add instead of the 64-bit multiply's four
+// scalar instructions.  The dispatch rule keeps every such offset below 2^31
+// (kPlainMaxEnvs).
+template <class T>
+__device__ __forceinline__ T *env_row32(T *base, int64_t e, int per) {
+    const uint32_t off = (uint32_t)e * (uint32_t)(per * (int)sizeof(T));
+    return (T *)((const char *)base + off);
+}
+// Lane 0's write-back of the per-env outputs: one 32-bit byte offset 4 e in a
+// VGPR shared by the four int32 arrays (global_store_dword voff, data,
+// s[base]), and e for the flags byte.
+__device__ __forceinline__ void plain_store_outputs(int64_t e, int32_t *__restrict__ timer,
+                                                    int32_t *__restrict__ reward, int32_t *__restrict__ n_new,
+                                                    int32_t *__restrict__ n_act, uint8_t *__restrict__ flags_out,
+                                                    int tnew, int elim, int nn, int na, int flags) {
+    uint32_t v4 = 4u * (uint32_t)e, v1 = (uint32_t)e;
+    TMG_OPAQUE_V(v4);
+    TMG_OPAQUE_V(v1);
+    *(int32_t *)((char *)timer + v4) = tnew;
+    *(int32_t *)((char *)reward + v4) = elim;
+    *(int32_t *)((char *)n_new + v4) = nn;
+    *(int32_t *)((char *)n_act + v4) = na;
+    *((uint8_t *)flags_out + v1) = (uint8_t)flags;
+}
+
 // TileMatchEnv.step for env e on one wave (tile_match_env.py:93-112).
 // GEN=false: lean variant for boards that can hold no special (no specials
 // enabled, cached effective mask trusted).  SBNB > 0 (<= 128 cells): the
@@ -2887,14 +2922,26 @@ __device__ __forceinline__ void store_rng(uint64_t *p, const Rng &g, int lane) {
 //      is left as with 0, and the call after it regenerates it instead of
 //      stepping (its action ignored, reward 0, not terminated).
 // Returns the ST_* bits this step raises for the sticky status word.
+//
+// PLAIN (plain_step_kernel, below): the call is known when the kernel is picked
+// to be trusted, with given actions and no fused output (plain_step,
+// tmg_dispatch.h), so those tests are compile-time here; the kernel's own
+// prologue has loaded the action, the timer and the mask bit and taken the
+// ineffective-move exit (`pre`), and an env's rows sit at 32-bit byte offsets.
 template <int MAXN, bool GEN, int SBNB, bool CODD, int TIER = TIER_MAIN, class WS = Ws<MAXN, GEN>,
-          class L = WsSerial<MAXN>, bool FIXED = false>
+          class L = WsSerial<MAXN>, bool FIXED = false, bool PLAIN = false>
 __device__ __forceinline__ uint32_t step_env(
     const Params &P, WS &w, int lane, int64_t e, int8_t *__restrict__ board, uint64_t *__restrict__ rng, int32_t *__restrict__ timer,
     const int32_t *__restrict__ actions, int32_t *__restrict__ reward, int32_t *__restrict__ n_new,
-    int32_t *__restrict__ n_act, uint8_t *__restrict__ flags_out, uint64_t *__restrict__ eff, int trust_eff,
-    int autoreset, L *lists) {
+    int32_t *__restrict__ n_act, uint8_t *__restrict__ flags_out, uint64_t *__restrict__ eff, int trust_eff_,
+    int autoreset, L *lists, const PlainPre *pre = nullptr) {
+    static_assert(!PLAIN || (!GEN && MAXN == 128 && SBNB > 0 && TIER == TIER_MAIN), "PLAIN: a lean bitboard step kernel");
     const int N = P.N, W = P.W;
+    const int trust_eff = PLAIN ? 1 : trust_eff_;
+// a fused output of Params (oh, vo_*): none is attached to a PLAIN call
+#define TMG_FUSED(f) (!PLAIN && P.f)
+// Params::num_moves (PLAIN: from the kernel's hot argument block)
+#define TMG_NUM_MOVES (PLAIN ? pre->num_moves : P.num_moves)
     // Only the 128-cell lean kernels regenerate a finished board inline
     // (autoreset 1 / 3); route_step (tmg_dispatch.h) hands every other kernel
     // autoreset 2 / 4, a masked reset_kernel launch after the step, so they
@@ -2904,15 +2951,22 @@ __device__ __forceinline__ uint32_t step_env(
     const bool regen_inline = autoreset == 1 || autoreset == 3;
     // wave-uniform loads (the action too with the in-kernel policy, where the
     // draw below replaces it: no wait for the flag before the load goes out)
-    int a = __builtin_amdgcn_readfirstlane(actions[e]);
-    const int t0 = __builtin_amdgcn_readfirstlane(timer[e]);
+    int a, t0;
+    if constexpr (PLAIN) {
+        a = pre->a; t0 = pre->t0;
+    } else {
+        a = __builtin_amdgcn_readfirstlane(actions[e]);
+        t0 = __builtin_amdgcn_readfirstlane(timer[e]);
+    }
     // Issued beside the two loads above, not depending on the action: the
     // env's cached mask row (lane i holds word i).  The ineffective-move exit
     // then waits for one memory latency instead of the chain action -> mask
     // word.  (The mask row is allocated memory whatever trust_eff says; it is
     // only read as a mask when trust_eff != 0.)  Loading the board and RNG
     // state there too measured slower: the quick waves wait for those loads.
-    const uint64_t effrow = lane < W ? eff[e * W + lane] : 0ULL;
+    uint64_t effrow = 0ULL;
+    if constexpr (!PLAIN) {
+    effrow = lane < W ? eff[e * W + lane] : 0ULL;
     TMG_KEEP_V(effrow);
     if (P.sample) {                                                         // the policy's action, from the mask
         a = __builtin_amdgcn_readfirstlane(sample_action(P, effrow, e, lane));
@@ -2929,7 +2983,7 @@ __device__ __forceinline__ uint32_t step_env(
 #ifndef TMG_QEXIT
 #define TMG_QEXIT 1
 #endif
-    if (TMG_QEXIT && trust_eff && t0 < P.num_moves - 1 && (unsigned)a < (unsigned)P.A) {
+    if (TMG_QEXIT && trust_eff && t0 < TMG_NUM_MOVES - 1 && (unsigned)a < (unsigned)P.A) {
         if (!((rdlane64(effrow, a >> 6) >> (a & 63)) & 1ULL)) {
             if (lane == 0) {
                 uint64_t ve = (uint64_t)e;
@@ -2938,49 +2992,56 @@ __device__ __forceinline__ uint32_t step_env(
                 reward[ve] = 0; n_new[ve] = 0; n_act[ve] = 0;
                 flags_out[ve] = (uint8_t)0;
                 if (P.vo_term) reinterpret_cast<uint32_t *>(P.vo_term)[ve] = 0u;
-                if (P.vo_left) P.vo_left[ve] = (int64_t)(P.num_moves - 1 - t0);
+                if (P.vo_left) P.vo_left[ve] = (int64_t)(TMG_NUM_MOVES - 1 - t0);
             }
             return 0;
         }
     }
+    }   // !PLAIN
     // an env that ended last call, with next-step autoreset: reset() now
     // (tested only inside the rare branch, so that the common path carries
     // no extra condition into the ineffective-move exit)
     bool pend = false;
-    if (t0 >= P.num_moves || a < 0 || a >= P.A) {                           // tile_match_env.py:94-95
-        pend = autoreset >= 3 && t0 >= P.num_moves;
+    if (t0 >= TMG_NUM_MOVES || a < 0 || a >= P.A) {                           // tile_match_env.py:94-95
+        pend = autoreset >= 3 && t0 >= TMG_NUM_MOVES;
     }
-    if (!pend && (t0 >= P.num_moves || a < 0 || a >= P.A)) {
+    if (!pend && (t0 >= TMG_NUM_MOVES || a < 0 || a >= P.A)) {
         if (lane == 0) {
             reward[e] = 0; n_new[e] = 0; n_act[e] = 0; flags_out[e] = FL_ERR;
-            store_vo(P, e, FL_ERR, t0);
+            if constexpr (!PLAIN) store_vo(P, e, FL_ERR, t0);
         }
-        if ((P.oh || P.vo_obs) && !trust_eff) {   // the fused outputs follow every board of an untrusted call
+        if ((TMG_FUSED(oh) || TMG_FUSED(vo_obs)) && !trust_eff) {   // the fused outputs follow every board of an untrusted call
             load_board(P, w, lane, board + e * 2 * N);
             WSYNC();
-            if (P.oh) store_onehot(P, w, lane, e);
-            if (P.vo_obs) store_obs(P, w, lane, e);
+            if (TMG_FUSED(oh)) store_onehot(P, w, lane, e);
+            if (TMG_FUSED(vo_obs)) store_obs(P, w, lane, e);
         }
         return ST_CALLER;
     }
-    int8_t *gb = board + e * 2 * N;
-    uint64_t *ge = eff + e * W;
+    int8_t *gb;
+    uint64_t *ge, *grng;
+    if constexpr (PLAIN) {
+        gb = env_row32(board, e, 2 * N); ge = env_row32(eff, e, W); grng = env_row32(rng, e, 5);
+    } else {
+        gb = board + e * 2 * N; ge = eff + e * W; grng = nullptr;
+    }
     const int t1 = t0 + 1;
-    const bool done = !pend && t1 == P.num_moves;                           // tile_match_env.py:100-101
+    const bool done = !pend && t1 == TMG_NUM_MOVES;                           // tile_match_env.py:100-101
     // envs regenerated in this call (here or by the reset launch after it)
     const bool regen = pend || (done && same);
     int flags = done ? FL_DONE : 0;
     bool effective = false;
     if (trust_eff && !pend) {                                               // board.py:352 via cached mask
-        effective = (rdlane64(effrow, a >> 6) >> (a & 63)) & 1ULL;
+        if constexpr (PLAIN) effective = pre->effective;
+        else effective = (rdlane64(effrow, a >> 6) >> (a & 63)) & 1ULL;
     }
     if (trust_eff && !effective && !(regen && regen_inline)) {              // no state change at all
         const bool defer = regen;                                           // reset_kernel next
         if (done && !same) {                                                // tile_match_env.py:119-120
             for (int i = lane; i < W; i += 64) ge[i] = 0ULL;
-            if (P.vo_mask) store_mask(P, w, lane, e, true);
+            if (TMG_FUSED(vo_mask)) store_mask(P, w, lane, e, true);
         }
-        if (done && same && P.vo_final) {                                   // the last board, as it stands
+        if (done && same && TMG_FUSED(vo_final)) {                                   // the last board, as it stands
             // dwords only when every env's board starts on a dword ((2N) % 4 == 0,
             // as `bwhole` below); an odd N gives 2-byte-aligned boards: bytes
             const int nbw = ((2 * N) & 3) == 0 ? (2 * N) >> 2 : 0;
@@ -2991,9 +3052,13 @@ __device__ __forceinline__ uint32_t step_env(
         }
         if (lane == 0) {
             const int tn = defer ? 0 : t1;
-            timer[e] = tn; reward[e] = 0; n_new[e] = 0; n_act[e] = 0;
-            flags_out[e] = (uint8_t)(flags | (defer ? FL_RESET : 0));
-            store_vo(P, e, flags, tn);
+            if constexpr (PLAIN) {
+                plain_store_outputs(e, timer, reward, n_new, n_act, flags_out, tn, 0, 0, 0, flags | (defer ? FL_RESET : 0));
+            } else {
+                timer[e] = tn; reward[e] = 0; n_new[e] = 0; n_act[e] = 0;
+                flags_out[e] = (uint8_t)(flags | (defer ? FL_RESET : 0));
+                store_vo(P, e, flags, tn);
+            }
         }
         return 0;
     }
@@ -3010,7 +3075,9 @@ __device__ __forceinline__ uint32_t step_env(
     const int nbw = (2 * N) >> 2;
     const bool bwhole = ((2 * N) & 3) == 0 && nbw <= 64;
     const uint32_t bw = bwhole ? reinterpret_cast<const uint32_t *>(gb)[lane < nbw ? lane : 0] : 0u;
-    const uint64_t *rp = rng + e * 5;
+    const uint64_t *rp;
+    if constexpr (PLAIN) rp = grng;
+    else rp = rng + e * 5;
     const uint64_t q0 = rp[0], q1 = rp[1], q2 = rp[2], q3 = rp[3], q4 = rp[4];
     // with rowp the rare users of the linear order below reload theirs (load_jump)
     bool rowp = false;
@@ -3032,7 +3099,7 @@ __device__ __forceinline__ uint32_t step_env(
         if (__ballot(!ok) != 0ULL) {
             if (lane == 0) {
                 reward[e] = 0; n_new[e] = 0; n_act[e] = 0; flags_out[e] = FL_ERR;
-                store_vo(P, e, FL_ERR, t0);
+                if constexpr (!PLAIN) store_vo(P, e, FL_ERR, t0);
             }
             return ST_INTERNAL;
         }
@@ -3054,7 +3121,7 @@ __device__ __forceinline__ uint32_t step_env(
             // board, sb_generate_exact after it where a word was rejected
             bool nolds = false;
             if constexpr (INLINE_GEN)
-                nolds = regen && regen_inline && P.C <= 32 && !P.vo_final && !P.oh && !P.vo_obs;
+                nolds = regen && regen_inline && P.C <= 32 && !TMG_FUSED(vo_final) && !TMG_FUSED(oh) && !TMG_FUSED(vo_obs);
             if (rowp) elim = rp_move<SBNB, CODD, kRpLevers>(P, w, lane, J, g, cl, p1, p2, flags, nolds);
             else elim = sb_move<SBNB, CODD>(P, w, lane, J, g, cl, p1, p2, flags, e);
         } else elim = board_move<MAXN, GEN, SBNB, CODD, TIER>(P, w, lane, J, g, cl, p1, p2, flags, nn, na, e, lists,
@@ -3077,7 +3144,7 @@ __device__ __forceinline__ uint32_t step_env(
     }
     int tnew = t1;
     if (regen) {                                                            // reset() without a seed
-        if (done && P.vo_final) store_board(P, w, lane, P.vo_final + e * 2 * N);   // same step: the last board
+        if (done && TMG_FUSED(vo_final)) store_board(P, w, lane, P.vo_final + e * 2 * N);   // same step: the last board
         if constexpr (INLINE_GEN) {
             if (regen_inline) {
                 int fg = -1;
@@ -3099,33 +3166,40 @@ __device__ __forceinline__ uint32_t step_env(
     }
     if (changed) {
         store_board(P, w, lane, gb);
-        store_rng(rng + e * 5, g, lane);
+        if constexpr (PLAIN) store_rng(grng, g, lane);
+        else store_rng(rng + e * 5, g, lane);
     }
     // fused one-hot planes: every board this step changed (or, with an
     // untrusted mask, any board: it may have been edited by hand)
-    if (P.oh && (changed || !trust_eff)) store_onehot(P, w, lane, e);
-    if (P.vo_obs && (changed || !trust_eff)) store_obs(P, w, lane, e);
+    if (TMG_FUSED(oh) && (changed || !trust_eff)) store_onehot(P, w, lane, e);
+    if (TMG_FUSED(vo_obs) && (changed || !trust_eff)) store_obs(P, w, lane, e);
     if (done && !same) {
         for (int i = lane; i < W; i += 64) ge[i] = 0ULL;                   // tile_match_env.py:119-120
-        if (P.vo_mask) store_mask(P, w, lane, e, true);
+        if (TMG_FUSED(vo_mask)) store_mask(P, w, lane, e, true);
     } else if (changed) {
         for (int i = lane; i < W; i += 64) ge[i] = w.effw[i];
-        if (P.vo_mask) store_mask(P, w, lane, e, false);
+        if (TMG_FUSED(vo_mask)) store_mask(P, w, lane, e, false);
     } else if (!trust_eff) {
         scan_effective(P, w, lane, cl, false);
         WSYNC();
         for (int i = lane; i < W; i += 64) ge[i] = w.effw[i];
-        if (P.vo_mask) store_mask(P, w, lane, e, false);
+        if (TMG_FUSED(vo_mask)) store_mask(P, w, lane, e, false);
     }
     if (lane == 0) {
-        timer[e] = tnew;
-        reward[e] = elim;
-        n_new[e] = nn;
-        n_act[e] = na;
-        flags_out[e] = (uint8_t)flags;
-        store_vo(P, e, flags, tnew);
+        if constexpr (PLAIN) {
+            plain_store_outputs(e, timer, reward, n_new, n_act, flags_out, tnew, elim, nn, na, flags);
+        } else {
+            timer[e] = tnew;
+            reward[e] = elim;
+            n_new[e] = nn;
+            n_act[e] = na;
+            flags_out[e] = (uint8_t)flags;
+            store_vo(P, e, flags, tnew);
+        }
     }
     return ((flags & FL_ERR) ? ST_INTERNAL : 0u) | ((flags & FL_OVF) ? ST_OVERFLOW : 0u);
+#undef TMG_FUSED
+#undef TMG_NUM_MOVES
 }
 
 // TileMatchEnv.step over a batch, one wave per env.
@@ -3211,6 +3285,98 @@ __global__ __launch_bounds__(64, MAXN == 128 ? (GEN ? kGen128Waves : (FIX != kNo
     if constexpr (GEN) lists = &w.s;
     const uint32_t st = step_env<MAXN, GEN, SBNB, CODD, TIER_MAIN, WS, WsSerial<MAXN>, FIX != kNoFix>(
         P, w, lane, e, board, rng, timer, actions, reward, n_new, n_act, flags_out, eff, trust_eff, autoreset, lists);
+    note_status(P, lane, st);
+}
+
+// The plain step of a fixed lean shape: step_kernel<128, false, NB, false, FIX>
+// for the calls plain_step (tmg_dispatch.h) accepts, that is trusted, with given
+// actions, no fused output, and few enough envs that every env's byte offset
+// fits 32 bits.  Those are facts of the launch, so the kernel carries no test
+// of them, and no code for the outputs and the policy.
+//
+// Most waves (76 % at c2, uniform actions) end in the ineffective-move exit,
+// which is written for the scalar unit, the kernel's busiest pipe:
+//   * what it needs sits in one block at the front of the kernarg (PlainHot,
+//     by value: loaded whole in the entry block), the env swizzle's block size
+//     included (wg_env reads it from the dispatch packet's grid size); Params
+//     follows and is first read after the exit;
+//   * the action, the timer and the three words of the mask row are scalar
+//     loads of one clause; the word is picked by compares, not by v_readlane;
+//   * lane 0 stores through plain_store_outputs and the wave ends there: its
+//     status is the constant 0, so it never reaches note_status.
+// autoreset stays a run-time argument; it is not read before the exit.
+struct PlainHot {
+    int32_t n;                  // envs of the launch (<= kPlainMaxEnvs)
+    int32_t per;                // gridDim.x / 8: envs per XCD block (wg_env)
+    int32_t last_move;          // Params::num_moves - 1: the timer of an episode's last move
+    int32_t autoreset;          // step_env's code: 0, or inline 1 / 3
+    const int32_t *actions;
+    int32_t *timer;
+    uint64_t *eff;
+    int32_t *reward, *n_new, *n_act;
+    uint8_t *flags;
+    int8_t *board;
+    uint64_t *rng;
+};
+static_assert(sizeof(PlainHot) % alignof(Params) == 0, "Params follows PlainHot in the kernarg segment unpadded");
+// Compiler-only marks, no instruction in any of them (the g++ build of the
+// host wave emulator has plain C++ in their place, as bp_merge): a use of three
+// wave-uniform values that yields them all (so all are loaded by then);
+// the wave's end (s_endpgm where it stands, not a jump to the kernel's common
+// tail).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TMG_PIN_S3(x, y, z) asm("" : "+s"(x), "+s"(y), "+s"(z))
+#define TMG_END_WAVE() __builtin_amdgcn_endpgm()
+#else
+#define TMG_PIN_S3(x, y, z) ((void)0)
+#define TMG_END_WAVE() return
+#endif
+#ifndef TMG_KERNARG_PARAMS_AT
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TMG_KERNARG_PARAMS_AT(p, off) \
+    (*(const Params *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + (off)))
+#else
+#define TMG_KERNARG_PARAMS_AT(p, off) (p)  // the host pass (never executed), and the host wave emulator
+#endif
+#endif
+
+template <int FIX>
+__global__ __launch_bounds__(64, kLean128Waves) void plain_step_kernel(PlainHot H, Params P_) {
+    constexpr int R = FIX >> 24, C = (FIX >> 16) & 255, K = (FIX >> 8) & 255;
+    constexpr int A = 2 * R * C - R - C, W = (A + 63) / 64;
+    static_assert(FIX != kNoFix && (FIX & 255) == 0 && R * C <= 128 && C <= 28 && !(C & 1) && W <= 3,
+                  "a lean row-plane shape with an even C and at most three mask words");
+    TMG_SMEM_DECL(smem);
+    using WS = Ws<128, false>;
+    const Params &P = TMG_KERNARG_PARAMS_AT(P_, sizeof(PlainHot));
+    assume_shape<FIX>(P);
+    const int lane = threadIdx.x & 63;
+    const uint32_t b = blockIdx.x;
+    const uint32_t e = (b & 7u) * (uint32_t)H.per + (b >> 3);               // wg_env
+    if (e >= (uint32_t)H.n) return;
+    // wave-uniform addresses, nothing stored yet: scalar loads of one clause,
+    // every word of the mask row whatever the action (one more wait otherwise)
+    const int a = __builtin_amdgcn_readfirstlane(*env_row32(H.actions, e, 1));
+    const int t0 = __builtin_amdgcn_readfirstlane(*env_row32(H.timer, e, 1));
+    const uint64_t *row = env_row32(H.eff, e, W);
+    uint64_t w0 = bcast64(row[0]), w1 = W > 1 ? bcast64(row[1]) : 0ULL, w2 = W > 2 ? bcast64(row[2]) : 0ULL;
+    TMG_PIN_S3(w0, w1, w2);
+    const uint64_t word = a < 64 ? w0 : a < 128 ? w1 : w2;
+    const uint32_t bit = (uint32_t)(word >> (a & 63)) & 1u;
+    // The common ineffective move (board.py:352-353): a live env, not the
+    // episode's last move, an action of the shape: only the timer and the zero
+    // outputs are written.
+    if (t0 < H.last_move && (unsigned)a < (unsigned)A && !bit) {
+        COVER(CV_PLAIN_EXIT);
+        if (lane == 0) plain_store_outputs(e, H.timer, H.reward, H.n_new, H.n_act, H.flags, t0 + 1, 0, 0, 0, 0);
+        TMG_END_WAVE();
+    }
+    COVER(CV_PLAIN_STEP);
+    WS &w = *reinterpret_cast<WS *>(smem);
+    const PlainPre pre{a, t0, H.last_move + 1, bit != 0u};
+    const uint32_t st = step_env<128, false, sb_planes(K), false, TIER_MAIN, WS, WsSerial<128>, true, true>(
+        P, w, lane, (int64_t)e, H.board, H.rng, H.timer, H.actions, H.reward, H.n_new, H.n_act, H.flags, H.eff, 1,
+        H.autoreset, (WsSerial<128> *)nullptr, &pre);
     note_status(P, lane, st);
 }
 

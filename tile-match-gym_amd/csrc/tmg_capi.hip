@@ -156,7 +156,7 @@ static int do_step(tmg_ctx *ctx, Params P, StepArgs a, hipStream_t s) {
         tmg::launch_step_lane(s, P, a);
     } else {
         switch (tmg::step_group(P, ctx->maxn, ctx->sb, r.lean)) {
-        case tmg::StepGroup::Lean128: tmg::launch_step_lean128(ctx->sb, grid, s, P, a); break;
+        case tmg::StepGroup::Lean128: tmg::launch_step_lean128(ctx->sb, r.plain, grid, s, P, a); break;
         case tmg::StepGroup::Gen128Even: tmg::launch_step_gen128_even(ctx->sb, grid, s, P, a); break;
         case tmg::StepGroup::Gen128Odd: tmg::launch_step_gen128_odd(grid, s, P, a); break;
         case tmg::StepGroup::Step512: tmg::launch_step512(!r.lean, grid, s, P, a); break;

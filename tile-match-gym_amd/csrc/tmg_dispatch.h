@@ -79,6 +79,30 @@ inline bool fused_output(const Params &P) {
 // boards; the general kernels take every other, with the spill tier behind.
 inline bool lean_step(const Params &P, int trust_eff) { return P.smask == 0 && trust_eff; }
 
+// whether P is the shape a FIX instantiation was compiled for
+template <int FIX>
+bool is_shape(const Params &P) {
+    const int sm = (FIX & 255) == kFixAnySpecials ? kFixAnySpecials : P.smask;
+    return shape_fix(P.R, P.C, P.k, sm) == FIX;
+}
+
+// The plain step kernel (plain_step_kernel, tmg_board.hip) takes the c2-shape
+// lean steps with given actions and no fused output: c2 and the c4 shard.  It
+// addresses an env's rows by 32-bit byte offsets, so the launch may hold at
+// most kPlainMaxEnvs envs: the widest rows are the board's 2 N bytes, the RNG
+// state's 40 and the mask's 8 W.
+constexpr int64_t kPlainMaxEnvs = 1 << 23;
+constexpr int64_t plain_max_offset(int R, int C) {      // the largest byte offset of a row's end, any array
+    const int64_t N = R * C, W = (2 * N - R - C + 63) / 64;
+    const int64_t row = 2 * N > 40 ? (2 * N > 8 * W ? 2 * N : 8 * W) : (40 > 8 * W ? 40 : 8 * W);
+    return kPlainMaxEnvs * row;
+}
+static_assert(plain_max_offset(kFixC2 >> 24, (kFixC2 >> 16) & 255) < (1LL << 31),
+              "every env's byte offset (e * 2N, e * 40, e * 8W, e * 4) stays below 2^31");
+inline bool plain_step(const Params &P, int trust_eff, int64_t n) {
+    return is_shape<kFixC2>(P) && lean_step(P, trust_eff) && !P.sample && !fused_output(P) && n <= kPlainMaxEnvs;
+}
+
 // Envs per wave of a reset_kernel launch: a masked reset (the deferred
 // autoreset after a step; most find no finished env) takes several, a full one
 // 1.  override > 0: the caller's own count for a masked launch.
@@ -95,6 +119,7 @@ inline bool sample_ahead(const Params &P, int trust_eff) {
 struct StepRoute {
     bool lean;              // lean_step: the lean kernels, not the general ones
     bool lane;             // the lane-per-board kernel instead of the wave-per-board ladder
+    bool plain;             // plain_step: the ladder's plain instantiation of the c2 kernel (never with lane)
     bool deferred;          // finished boards are left to a reset launch masked by FL_RESET
     bool spill;             // spill_kernel follows (the general kernels: steps that ran out of LDS lists)
     int kernel_autoreset;   // the kernel's code (step_env): 0 none, 1 / 3 inline, 2 / 4 deferred
@@ -111,6 +136,7 @@ inline StepRoute route_step(const Params &P, int maxn, int trust_eff, int mode, 
     r.lean = lean_step(P, trust_eff);
     r.lane = have_lane && kLaneKernel && r.lean && maxn == 128 && lane_shape(P) && !fused_output(P) &&
              (P.sample || n >= kLaneMinEnvs);
+    r.plain = !r.lane && maxn == 128 && plain_step(P, trust_eff, n);
     r.deferred = mode && (maxn == 512 || !r.lean || r.lane);
     r.spill = !r.lean;
     r.kernel_autoreset = mode == 0 ? 0 : mode == 1 ? (r.deferred ? 2 : 1) : (r.deferred ? 4 : 3);
@@ -131,13 +157,6 @@ inline StepGroup step_group(const Params &P, int maxn, bool sb, bool lean) {
 // One per launcher group; each calls exactly one member of the launcher, and
 // names only its own group's instantiations.
 
-// whether P is the shape a FIX instantiation was compiled for
-template <int FIX>
-bool is_shape(const Params &P) {
-    const int sm = (FIX & 255) == kFixAnySpecials ? kFixAnySpecials : P.smask;
-    return shape_fix(P.R, P.C, P.k, sm) == FIX;
-}
-
 // scalar-bitboard step variants: NB colour planes (sb_planes(k))
 template <bool GEN, bool CODD, class L>
 void step_sb_ladder(const Params &P, L &l) {
@@ -149,9 +168,12 @@ void step_sb_ladder(const Params &P, L &l) {
     }
 }
 
+// plain: StepRoute::plain; step_plain<FIX>() starts plain_step_kernel<FIX>,
+// the plain form of step<128, false, 2, false, FIX>
 template <class L>
-void step_lean128_ladder(const Params &P, bool sb, L &l) {
+void step_lean128_ladder(const Params &P, bool sb, L &l, bool plain = false) {
     if (!sb) l.template step<128, false, 0, false, kNoFix>();
+    else if (is_shape<kFixC2>(P) && plain) l.template step_plain<kFixC2>();
     else if (is_shape<kFixC2>(P)) l.template step<128, false, 2, false, kFixC2>();
     else if (P.C & 1) step_sb_ladder<false, true>(P, l);
     else step_sb_ladder<false, false>(P, l);
@@ -240,9 +262,9 @@ void effective512_ladder(L &l) { l.template effective<512>(); }
 // The whole rule for a caller that holds every group at once (the emulator;
 // the library's groups sit behind the launch_* functions of tmg_launch.h).
 template <class L>
-void step_ladder(const Params &P, int maxn, bool sb, bool lean, L &l) {
+void step_ladder(const Params &P, int maxn, bool sb, bool lean, L &l, bool plain = false) {
     switch (step_group(P, maxn, sb, lean)) {
-    case StepGroup::Lean128: step_lean128_ladder(P, sb, l); break;
+    case StepGroup::Lean128: step_lean128_ladder(P, sb, l, plain); break;
     case StepGroup::Gen128Even: step_gen128_even_ladder(P, sb, l); break;
     case StepGroup::Gen128Odd: step_gen128_odd_ladder(P, l); break;
     case StepGroup::Step512: step512_ladder(P, !lean, l); break;

@@ -47,6 +47,13 @@ struct StepLaunch {
         hipLaunchKernelGGL((step_kernel<MAXN, GEN, NB, CODD, FIX>), grid, dim3(64), lds, s, P, a.n, a.board, a.rng,
                            a.timer, a.actions, a.reward, a.n_new, a.n_act, a.flags, a.eff, a.trust_eff, a.autoreset);
     }
+    template <int FIX>
+    void step_plain() {
+        const size_t lds = sizeof(Ws<128, false>);
+        const PlainHot H{(int32_t)a.n, (int32_t)(grid.x >> 3), P.num_moves - 1, a.autoreset, a.actions, a.timer, a.eff,
+                         a.reward, a.n_new, a.n_act, a.flags, a.board, a.rng};
+        hipLaunchKernelGGL((plain_step_kernel<FIX>), grid, dim3(64), lds, s, H, P);
+    }
 };
 
 template <int MAXN>
@@ -290,9 +297,9 @@ void launch_step_lane(hipStream_t s, const Params &P, const StepArgs &a) {
     else small ? lane_one<5, 32>(s, P, a) : lane_one<5, 64>(s, P, a);
 }
 
-void launch_step_lean128(bool sb, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
+void launch_step_lean128(bool sb, bool plain, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a) {
     StepLaunch l{grid, s, P, a};
-    step_lean128_ladder(P, sb, l);
+    step_lean128_ladder(P, sb, l, plain);
 }
 #endif
 

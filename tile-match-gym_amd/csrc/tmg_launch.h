@@ -29,8 +29,8 @@ struct StepArgs {
 dim3 env_grid(int64_t n);
 
 // TU 1 — lean step kernels (no specials, cached mask trusted), <= 128 cells;
-// sb: scalar-bitboard variants (C <= 63)
-void launch_step_lean128(bool sb, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a);
+// sb: scalar-bitboard variants (C <= 63); plain: StepRoute::plain (tmg_dispatch.h)
+void launch_step_lean128(bool sb, bool plain, dim3 grid, hipStream_t s, const Params &P, const StepArgs &a);
 // and the lane-per-board lean step (tmg_lane.h) for the shapes lane_shape
 // (tmg_dispatch.h) accepts; its autoreset codes are the deferred ones (0, 2, 4)
 void launch_step_lane(hipStream_t s, const Params &P, const StepArgs &a);

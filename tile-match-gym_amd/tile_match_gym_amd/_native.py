@@ -41,7 +41,8 @@ COVER_NAMES = ("sb_lean", "sb_normal", "sb_laser", "sb_perp_bomb", "sb_row_bomb"
                "lane_step", "lane_shuffle", "lane_redraw", "lane_reject", "lane_reject_redraw",
                "rp_carry", "rp_rebatch", "peek_move", "peek_spill", "peek_spill_run",
                "roll_ply", "roll_horizon", "roll_spill", "roll_spill_run",
-               "bp_pair_acc", "bp_pair_rej", "rp_vshift", "rp_vmore", "rp_scan2", "bp_round_carry", "rp_nolds")
+               "bp_pair_acc", "bp_pair_rej", "rp_vshift", "rp_vmore", "rp_scan2", "bp_round_carry", "rp_nolds",
+               "plain_exit", "plain_step")
 
 SPECIAL_BITS = {"cookie": 1, "vertical_laser": 2, "horizontal_laser": 4, "bomb": 8}
 FLAG_DONE, FLAG_COMBO, FLAG_SHUFFLED, FLAG_RESET, FLAG_OVERFLOW, FLAG_ERROR = 1, 2, 4, 8, 0x40, 0x80

@@ -249,6 +249,13 @@ struct EmuStep {
     void step() {
         run_blocks(n, sizeof(tmg::Ws<MAXN, GEN>), [&] { tmg::step_kernel<MAXN, GEN, NB, CODD, FIX>(P, n, board, rng, timer, actions, reward, n_new, n_act, flags, eff, trust_eff, autoreset); });
     }
+    template <int FIX>
+    void step_plain() {
+        const int64_t grid = (n + 7) & ~(int64_t)7;                    // run_blocks' padding
+        const tmg::PlainHot H{(int32_t)n, (int32_t)(grid >> 3), P.num_moves - 1, autoreset, actions, timer, eff,
+                              reward, n_new, n_act, flags, board, rng};
+        run_blocks(n, sizeof(tmg::Ws<128, false>), [&] { tmg::plain_step_kernel<FIX>(H, P); });
+    }
     template <int MAXN>
     void spill() {
         run_grid(tmg::kSpillWaves, sizeof(tmg::Ws<MAXN, false>), [&] { tmg::spill_kernel<MAXN>(P, n, board, rng, timer, actions, reward, n_new, n_act, flags, eff, trust_eff, autoreset); });
@@ -333,6 +340,9 @@ struct Recorder {
     int *out;
     template <int MAXN, bool GEN, int NB, bool CODD, int FIX>
     void step() { out[0] = MAXN; out[1] = GEN; out[2] = NB; out[3] = CODD; out[4] = FIX; }
+    // the plain form of step<128, false, NB, false, FIX>: the same instantiation tuple (StepRoute::plain tells them apart)
+    template <int FIX>
+    void step_plain() { out[0] = 128; out[1] = 0; out[2] = tmg::sb_planes((FIX >> 8) & 255); out[3] = 0; out[4] = FIX; }
     template <int MAXN, int NB, bool CODD, int FIX>
     void reset() { out[0] = MAXN; out[1] = NB; out[2] = CODD; out[3] = FIX; }
     template <int MAXN, bool GEN, int NB, bool CODD>
@@ -363,7 +373,7 @@ int emu_step(int R, int C, int k, int smask, int moves, int64_t n, int8_t *board
     const int maxn = tmg::shape_maxn(P);
     const tmg::StepRoute r = tmg::route_step(P, maxn, trust_eff, autoreset, n, false);
     EmuStep S{P, n, board, rng, timer, actions, reward, n_new, n_act, flags, eff, trust_eff, r.kernel_autoreset};
-    tmg::step_ladder(P, maxn, tmg::shape_sb(P), r.lean, S);
+    tmg::step_ladder(P, maxn, tmg::shape_sb(P), r.lean, S, r.plain);
     if (r.spill) {
         if (maxn == 128) S.spill<128>();
         else S.spill<512>();
@@ -375,9 +385,9 @@ int emu_step(int R, int C, int k, int smask, int moves, int64_t n, int8_t *board
 
 // What the rule picks for a step and for a reset of one call, nothing run.
 // fused: bit 0 the one-hot output, bits 1..5 vo_term / vo_mask / vo_left /
-// vo_final / vo_obs.  step[11]: MAXN, GEN, NB, CODD, FIX of the step kernel
+// vo_final / vo_obs.  step[12]: MAXN, GEN, NB, CODD, FIX of the step kernel
 // (all 0 when the lane kernel takes the step), then lean, lane, deferred,
-// kernel_autoreset, spill, reset_epw.  reset[6]: MAXN, NB, CODD, FIX of the
+// kernel_autoreset, spill, reset_epw, plain.  reset[6]: MAXN, NB, CODD, FIX of the
 // reset kernel, then the envs per wave of a full and of a masked reset.
 int emu_route(int R, int C, int k, int smask, int trust_eff, int mode, int64_t n, int have_lane, int policy, int fused,
               int *step, int *reset) {
@@ -395,9 +405,9 @@ int emu_route(int R, int C, int k, int smask, int trust_eff, int mode, int64_t n
     const tmg::StepRoute r = tmg::route_step(P, maxn, trust_eff, mode, n, have_lane != 0);
     for (int i = 0; i < 5; i++) step[i] = 0;
     Recorder rs{step}, rr{reset};
-    if (!r.lane) tmg::step_ladder(P, maxn, sb, r.lean, rs);
+    if (!r.lane) tmg::step_ladder(P, maxn, sb, r.lean, rs, r.plain);
     step[5] = r.lean; step[6] = r.lane; step[7] = r.deferred; step[8] = r.kernel_autoreset; step[9] = r.spill;
-    step[10] = r.reset_epw;
+    step[10] = r.reset_epw; step[11] = r.plain;
     tmg::reset_ladder(P, maxn, sb, rr);
     reset[4] = tmg::reset_envs_per_wave(maxn, false);
     reset[5] = tmg::reset_envs_per_wave(maxn, true);

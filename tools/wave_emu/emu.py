@@ -42,7 +42,8 @@ def load(asan=False):
     return L
 
 
-STEP_ROUTE = ("MAXN", "GEN", "NB", "CODD", "FIX", "lean", "lane", "deferred", "kernel_autoreset", "spill", "reset_epw")
+STEP_ROUTE = ("MAXN", "GEN", "NB", "CODD", "FIX", "lean", "lane", "deferred", "kernel_autoreset", "spill", "reset_epw",
+              "plain")
 RESET_ROUTE = ("MAXN", "NB", "CODD", "FIX", "epw_full", "epw_masked")
 FUSED = ("onehot", "terminated", "action_mask", "moves_left", "final_board", "board32")
 

@@ -97,7 +97,13 @@ TMG_API int tmg_reset(tmg_ctx *ctx, int64_t n, int8_t *board, uint64_t *rng, int
  *   (continuing its RNG stream, == reset() without a seed); reward / flags
  *   still describe the final move and flag bit3 is set.  With autoreset == 0
  *   a finished env writes an all-zero eff mask (tile_match_env.py:119-120) and
- *   a further step sets TMG_FLAG_ERROR without touching its state. */
+ *   a further step sets TMG_FLAG_ERROR without touching its state.
+ * The type plane: with no special enabled and trust_eff != 0, every
+ *   wave-per-board launch verifies it (a non-normal tile sets TMG_FLAG_ERROR
+ *   for that env, leaves its board, RNG words and timer untouched and raises
+ *   TMG_STATUS_INTERNAL), while the lane-per-board launch (10x10 boards of 4
+ *   or 5 colours, under the in-kernel policy or from 131072 envs on) reads
+ *   only the colour plane and relies on the caller. */
 TMG_API int tmg_step(tmg_ctx *ctx, int64_t n, int8_t *board, uint64_t *rng, int32_t *timer,
              const int32_t *actions, int32_t *reward, int32_t *n_new, int32_t *n_act,
              uint8_t *flags, uint64_t *eff, int trust_eff, int autoreset, void *stream);
